@@ -18,6 +18,12 @@ collective) while the next segment is stepped; the line reports the throughput w
 without it.  `--config 3|4|5` runs BASELINE.json's other configs at their TOTAL sizes divided over the
 GPUs (strong scaling).
 Prints ONE JSON line on rank 0.
+
+A plain run sets up, pre-rolls, warms up, times the K steps and prints the headline (with the kernel time of the timed launches).
+`--full` adds every secondary measurement and check after the timed region: the multi-rank hand-off and north_star blocks, the
+segment-launch, walking-gait and closed-loop workloads, the launch-rate probe, the CPU baselines and the comparisons with the oracle
+and the recorded PyBullet episodes.  `--dump-outputs DIR` writes what the last timed step returned (rank 0's shard: obs, reward,
+done) as DIR/<name>.npy; the inputs are seeded, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -456,21 +462,29 @@ def main():
                                                          "+ per-env mass x U(0.8,1.2) / foot friction 0.5 x U(0.5,1.25)")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl = RCCL; gloo only to smoke-test the "
                                                       "multi-rank path on a box with fewer GPUs than ranks)")
+    ap.add_argument("--full", action="store_true", help="after the timed region, run every secondary measurement and check as well "
+                                                        "(the --no-* switches above apply to them); a plain run prints the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the observation / reward / done of the last timed step "
+                                                                         "(rank 0's shard) as DIR/<name>.npy, float32")
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit("--steps must be at least 1")
 
-    import torch
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # `python bench.py --gpus N`: start the N ranks ourselves (one process per GPU, rendezvous on 127.0.0.1) -- the same
-        # command line under torch.distributed.run; rank 0 prints the one JSON line
+        # command line under torch.distributed.run, in a child process; rank 0 prints the one JSON line
         import socket
+        import subprocess
         with socket.socket() as sock:
             sock.bind(("127.0.0.1", 0))
             port = sock.getsockname()[1]
-        os.execv(sys.executable, [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}",
-                                  "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:])
+        rc = subprocess.call([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}",
+                              "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:])
+        raise SystemExit(rc)
+    import torch
     if world != args.gpus:
         raise SystemExit(f"--gpus {args.gpus} but WORLD_SIZE={world}: launch with torch.distributed.run --nproc-per-node {args.gpus} "
                          "(or without it: bench.py starts its own ranks)")
@@ -536,6 +550,14 @@ def main():
     timed_launch_steps = list(ro.launch_steps)           # (--segment-launch: the env steps behind each of those durations)
     kms = sorted(kms_raw)
     env.set_timing(False)
+    if args.dump_outputs and rank == 0:
+        # what the last timed step handed its caller: slice t of the rollout segment it wrote (before anything below steps again)
+        import numpy as np
+        k = ro.clock - 1
+        last = seg[(k // T) & 1]
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name in ("obs", "reward", "done"):
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), last[name][k % T].float().cpu().numpy())
     if dist is not None:
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev if args.backend == "nccl" else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -543,7 +565,7 @@ def main():
 
     # the same K steps without the hand-off, and the hand-off on its own (blocking, nothing to overlap with): N > 1 only
     gather_info = None
-    if dist is not None and do_gather:
+    if args.full and dist is not None and do_gather:
         barrier()
         t1 = time.perf_counter()
         run(args.steps, False)
@@ -567,7 +589,7 @@ def main():
 
     # north_star's own multi-GPU workload next to the weak-scaling line (default workload, N > 1 only)
     north_star = None
-    if dist is not None and do_gather and args.config is None and args.envs_per_gpu is None and not args.mixed \
+    if args.full and dist is not None and do_gather and args.config is None and args.envs_per_gpu is None and not args.mixed \
             and (args.task, args.signal, args.terrain, args.mark) == ("walk", "ik", "plane", "base"):
         north_star = north_star_workload(args, dev, local_rank, rank, world, dist, barrier, T)
 
@@ -576,7 +598,7 @@ def main():
     # rollouts draw them a segment ahead -- does not have to.  Same steps, same results bit for bit; what changes is that a wave goes on
     # to its envs' next step without waiting for the slowest wave of every step.
     segment_launch = None
-    if not args.no_segment_launch and not args.segment_launch:
+    if args.full and not args.no_segment_launch and not args.segment_launch:
         # (its own step counts: at least 8 launches of each segment length, however short the timed region above was)
         steps_seg, steps_seg4 = max(args.steps, 8 * T), max(args.steps, 32 * T)
         run(2 * T - ro.clock % T, do_gather, True)          # (up to a segment boundary: the timed launches below are whole segments)
@@ -615,22 +637,25 @@ def main():
                                   "(tests/test_gpu_parity.py::test_segment_launch_is_bit_identical_to_single_steps)"}
 
     # does this sim regroup its envs every step?  (two sorting launches behind each step kernel, outside kernel_ms: include/rexsim.h)
-    probe = torch.empty(n, dtype=torch.int32, device=dev)
-    regroups = env._L.rex_get_sweeps(env._h, probe.data_ptr(), env._stream_ptr()) == 0
-    del probe
+    regroups = launch_ms = None
+    if args.full:
+        probe = torch.empty(n, dtype=torch.int32, device=dev)
+        regroups = env._L.rex_get_sweeps(env._h, probe.data_ptr(), env._stream_ptr()) == 0
+        del probe
 
     # Launch duration of the dominant kernel over the TIMED launches: device-side timestamps (rex_set_timing(3)): first-wave
     # start to last-wave end of each launch -- the kernel alone, comparable with rocprofv3's kernel trace (profiles/).
     # launch_ms: two HIP events around m back-to-back launches / m on the launch stream (RexBatchEnv launches on torch's
-    # current stream, so torch.cuda.Event records on that very stream) -- the kernel plus the dispatch hand-over.
+    # current stream, so torch.cuda.Event records on that very stream) -- the kernel plus the dispatch hand-over (--full only).
     m = min(256, max(20, args.steps // 8))
-    ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    ev0.record(torch.cuda.current_stream(dev))
-    for k in range(m):
-        env.step(acts[k % T])      # (launch-rate probe: one pre-drawn segment of actions, recycled)
-    ev1.record(torch.cuda.current_stream(dev))
-    ev1.synchronize()
-    launch_ms = ev0.elapsed_time(ev1) / m
+    if args.full:
+        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        ev0.record(torch.cuda.current_stream(dev))
+        for k in range(m):
+            env.step(acts[k % T])      # (launch-rate probe: one pre-drawn segment of actions, recycled)
+        ev1.record(torch.cuda.current_stream(dev))
+        ev1.synchronize()
+        launch_ms = ev0.elapsed_time(ev1) / m
     if not kms:
         env.set_timing(3)
         for k in range(m):
@@ -667,7 +692,7 @@ def main():
     # which the reference's gait -- driven by time.time(), gait_planner.py:108-110 -- walks instead of falling after ~240
     # steps): reported next to the headline, never instead of it
     walking = None
-    if world == 1 and not args.mixed and not args.no_walking_workload and args.signal == "ik" and args.task in ("walk", "turn", "gallop"):
+    if args.full and world == 1 and not args.mixed and not args.no_walking_workload and args.signal == "ik" and args.task in ("walk", "turn", "gallop"):
         env2 = RexBatchEnv(n, device=local_rank, seed=0, env_index_base=rank * n, auto_reset=True, max_episode_steps=2000,
                            gait_clock_scale=1.5, check_actions=False, **env_kw)
         env2.reset()
@@ -686,7 +711,7 @@ def main():
 
     # the rollout a PPO learner runs: the policy in the loop (single-task workloads; the toes-only kernels carry the fused actor)
     closed_loop = None
-    if not args.mixed and not args.no_closed_loop and not body_contacts:
+    if args.full and not args.mixed and not args.no_closed_loop and not body_contacts:
         if dist is None:
             try:
                 closed_loop = closed_loop_workload(n, dev, local_rank, rank, env_kw, max(args.steps, 200), T)
@@ -732,7 +757,7 @@ def main():
                          "kernel": "rex_step_kernel", "kernel_ms": kernel_ms, "kernel_ms_min": kms[0],
                          "kernel_ms_over": f"{len(kms)} of the {args.steps} timed launches" if not args.no_device_timing else f"{len(kms)} launches after the timed region",
                          "launch_ms": launch_ms,
-                         "regroup_launches_ms": (launch_ms - kernel_ms) if regroups else None,   # the per-step sort of a regrouped batch: in launch_ms and ms_per_step, not in kernel_ms
+                         "regroup_launches_ms": (launch_ms - kernel_ms) if regroups and launch_ms is not None else None,   # the per-step sort of a regrouped batch: in launch_ms and ms_per_step, not in kernel_ms
                          "algorithmic_bytes_per_env_step": algo_bytes,
                          "layout_bytes_per_env_step": layout_bytes(state_words, act_dim, obs_dim),
                          "note": "the fused step is bound by the VALU issue rate of one wave per SIMD through the sequential "
@@ -756,7 +781,7 @@ def main():
             out["walking_gait_workload"] = walking
         if closed_loop:
             out["closed_loop"] = closed_loop
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             if not args.mixed:
                 try:   # SURVEY.md 8(d) baseline (ii): the CPU restatement on all granted threads and on one
                     out["cpu_baseline"] = cpu_baseline(args.task, args.signal, args.mark, n)

@@ -2028,6 +2028,7 @@ ORC_API void orc_physics_substep(real* st, const real* tau, real dt, int iterati
 ORC_API void orc_forward_dynamics(const real* st, const real* tau, real* out) {
   Phys p;
   static __thread Aba A;
+  MASS_SCALE_BASE = 1; MASS_SCALE_LEG = 1;   /* the robot as built (an env step leaves this thread's scales at its last env's draw) */
   memcpy(p.pos, st, sizeof(real) * 3); memcpy(p.quat, st + 3, sizeof(real) * 4);
   memcpy(p.linvel, st + 7, sizeof(real) * 3); memcpy(p.angvel, st + 10, sizeof(real) * 3);
   memcpy(p.q, st + 13, sizeof(real) * NJ); memcpy(p.qd, st + 13 + NJ, sizeof(real) * NJ);
@@ -2039,6 +2040,7 @@ ORC_API void orc_energy_momentum(const real* st, real* out /* E, px, py, pz */) 
   Phys p;
   static __thread Aba A;
   real tau[NJ] = {0}, qdd[NJ], wd[3], vd[3];
+  MASS_SCALE_BASE = 1; MASS_SCALE_LEG = 1;   /* as orc_forward_dynamics */
   memcpy(p.pos, st, sizeof(real) * 3); memcpy(p.quat, st + 3, sizeof(real) * 4);
   memcpy(p.linvel, st + 7, sizeof(real) * 3); memcpy(p.angvel, st + 10, sizeof(real) * 3);
   memcpy(p.q, st + 13, sizeof(real) * NJ); memcpy(p.qd, st + 13 + NJ, sizeof(real) * NJ);

@@ -1,11 +1,13 @@
 """TF-1 checkpoint reader and the policy player ("a loader for the shipped TF1 checkpoints").
 
 The reader is checked (a) against a tensor bundle written here with the documented table format -- including prefix
-compressed keys, several data blocks and a snappy block -- and (b), when the reference tree is present (the build
-container; it does not exist on the GPU box), against every checkpoint the reference ships: all tensors pass their stored
+compressed keys, several data blocks and a snappy block -- and (b) against every checkpoint the reference ships (stored
+under tests/golden/policies/, tests/golden/make_policy_golden.py): all tensors pass their stored
 crc32c, the layer sizes are the ones the policy's config.yaml names, and the restored policy maps observations inside
 the env's bounds to actions inside the env's bounds."""
+import lzma
 import os
+import shutil
 import struct
 import types
 
@@ -17,7 +19,27 @@ from rex_gym_amd.agents import policy_player, tf_checkpoint
 from rex_gym_amd.agents.tf_checkpoint import Checkpoint, CheckpointError, masked_crc32c
 from rex_gym_amd.envs.spaces import Box
 
-REFERENCE = os.environ.get("REX_REFERENCE", "/root/reference")
+# the reference's shipped checkpoints (their tensor bundles; .data shards xz-compressed): tests/golden/make_policy_golden.py
+GOLDEN_POLICIES = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "policies")
+# stored with their episode memory (memory/*) zeroed in place, to keep the fixture small: every other tensor as shipped
+MASKED = {"walk/ik/model.ckpt-2000000", "turn/ik/model.ckpt-2000000"}
+
+
+@pytest.fixture(scope="module")
+def policies(tmp_path_factory):
+    """tests/golden/policies/ unpacked into a temporary directory: the checkpoint files as the reference ships them"""
+    root = str(tmp_path_factory.mktemp("policies"))
+    for dirpath, _, files in os.walk(GOLDEN_POLICIES):
+        for name in files:
+            src = os.path.join(dirpath, name)
+            dst = os.path.join(root, os.path.relpath(src, GOLDEN_POLICIES))
+            os.makedirs(os.path.dirname(dst), exist_ok=True)
+            if name.endswith(".xz"):
+                with lzma.open(src) as f, open(dst[:-3], "wb") as g:
+                    shutil.copyfileobj(f, g)
+            else:
+                shutil.copyfile(src, dst)
+    return root
 
 
 # ---------------------------------------------------------------- a writer for the same format (test side only)
@@ -212,13 +234,12 @@ SHIPPED = {   # util/flag_mapper.py:1-10; obs / action sizes of the env each pol
 }
 
 
-@pytest.mark.skipif(not os.path.isdir(os.path.join(REFERENCE, "rex_gym", "policies")), reason="reference tree not present")
 @pytest.mark.parametrize("rel", sorted(SHIPPED))
-def test_shipped_reference_policies_load(rel):
-    prefix = os.path.join(REFERENCE, "rex_gym", "policies", rel)
+def test_shipped_reference_policies_load(rel, policies):
+    prefix = os.path.join(policies, rel)
     ck = Checkpoint(prefix)
     for name in ck.names():
-        if name.startswith(("network/", "normalize_")):
+        if not (rel in MASKED and name.startswith("memory/")):     # (zeroed in the fixture: tests/golden/make_policy_golden.py)
             ck.tensor(name)                                        # crc32c verified
     net = policy_player.restore_network(ck)
     obs_dim, act_dim = SHIPPED[rel]
@@ -230,10 +251,9 @@ def test_shipped_reference_policies_load(rel):
     assert bool(torch.isfinite(mean).all()) and bool((mean.abs() <= 1).all()) and bool(torch.isfinite(value).all())
 
 
-@pytest.mark.skipif(not os.path.isdir(os.path.join(REFERENCE, "rex_gym", "policies")), reason="reference tree not present")
-def test_checkpoints_whose_data_shard_is_missing_fail_loudly():
+def test_checkpoints_whose_data_shard_is_missing_fail_loudly(policies):
     """gallop/ik, gallop/ol and walk/ol ship their .index but not their .data (repository size limits)."""
-    ck = Checkpoint(os.path.join(REFERENCE, "rex_gym", "policies", "walk", "ol", "model.ckpt-4000000"))
+    ck = Checkpoint(os.path.join(policies, "walk", "ol", "model.ckpt-4000000"))
     assert "network/rnn/policy/logstd" in ck.entries
     if not os.path.exists(ck.prefix + ".data-00000-of-00001"):
         with pytest.raises(CheckpointError, match="shard missing"):
@@ -282,12 +302,11 @@ def test_save_policy_is_the_inverse_of_the_restore_functions(tmp_path):
                        policy_player.SimplePPOPolicy(env, ck).get_action(torch.zeros(3, 4)))
 
 
-@pytest.mark.skipif(not os.path.isdir(os.path.join(REFERENCE, "rex_gym", "policies")), reason="reference tree not present")
-@pytest.mark.parametrize("rel", sorted(SHIPPED))
-def test_rewritten_shipped_checkpoints_are_byte_identical(rel, tmp_path):
-    """TensorFlow's own output is the golden vector of the writer: every shipped checkpoint, read and written again, gives the
-    shipped .index and .data files byte for byte (table block layout, restart points, entry protos, checksums, footer)."""
-    prefix = os.path.join(REFERENCE, "rex_gym", "policies", rel)
+@pytest.mark.parametrize("rel", sorted(set(SHIPPED) - MASKED))
+def test_rewritten_shipped_checkpoints_are_byte_identical(rel, tmp_path, policies):
+    """TensorFlow's own output is the golden vector of the writer: every shipped checkpoint stored whole, read and written again, gives
+    the shipped .index and .data files byte for byte (table block layout, restart points, entry protos, checksums, footer)."""
+    prefix = os.path.join(policies, rel)
     ck = Checkpoint(prefix)
     out = tf_checkpoint.write_checkpoint(str(tmp_path / "again"), {n: ck.tensor(n) for n in ck.names()})
     for ext in (".index", ".data-00000-of-00001"):
@@ -295,14 +314,13 @@ def test_rewritten_shipped_checkpoints_are_byte_identical(rel, tmp_path):
             assert f.read() == g.read(), ext
 
 
-@pytest.mark.skipif(not os.path.isdir(os.path.join(REFERENCE, "rex_gym", "policies")), reason="reference tree not present")
-def test_restored_network_reproduces_the_reference_graphs_recorded_outputs():
+def test_restored_network_reproduces_the_reference_graphs_recorded_outputs(policies):
     """Outputs of the reference's own TensorFlow graph to hold the restored network and filter to: the turn / ol checkpoint was saved between two
     PPO updates, so its episode memory (`memory/Variable_1` observ, `_3` mean, `_4` logstd; agents/ppo/algorithm.py:66-78,126-133) holds what
     `perform()` computed for the episodes collected since the last update -- with the very weights the checkpoint stores (episodes whose recorded
     logstd is the checkpoint's; the others are leftovers of an earlier cycle).  The observ filter kept streaming while they were collected
     (1e6 samples seen, so it barely moved): the recomputed mean action agrees to 2e-3 where the leftovers are 1e-1 off."""
-    ck = Checkpoint(os.path.join(REFERENCE, "rex_gym", "policies", "turn", "ol", "model.ckpt-2000000"))
+    ck = Checkpoint(os.path.join(policies, "turn", "ol", "model.ckpt-2000000"))
     net = policy_player.restore_network(ck).eval()
     filt = policy_player.restore_normalizer(ck, "normalize_observ", clip=5.0)
     length, observ = ck.tensor("memory/Variable"), ck.tensor("memory/Variable_1")

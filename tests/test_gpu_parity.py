@@ -750,12 +750,12 @@ def test_ppo_learner_runs_on_the_batch_env_tensors(torch):
 
 
 def test_bench_prints_one_json_line_with_the_contract_fields(torch):
-    """bench.py --gpus 1 with a short run: ONE JSON line carrying the driver's contract fields, the roofline object
-    and (bounded) the CPU baseline of the oracle."""
+    """bench.py --gpus 1 --full with a short run: ONE JSON line carrying the driver's contract fields, the roofline object
+    and the secondary measurements."""
     import json, os, subprocess, sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "60", "--warmup", "20",
-                          "--no-cpu-baseline"], capture_output=True, text=True, timeout=600, cwd=root)
+                          "--no-cpu-baseline", "--full"], capture_output=True, text=True, timeout=600, cwd=root)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.strip().startswith("{")]
     assert len(lines) == 1
@@ -784,6 +784,34 @@ def test_bench_prints_one_json_line_with_the_contract_fields(torch):
     assert len(r["csrc_sha16"]) == 16 and "traffic_library_commit" in r and "traffic_is_of_this_library" in r
 
 
+def test_plain_bench_run_is_the_headline_and_dumps_the_last_steps_outputs(torch, tmp_path):
+    """bench.py without --full: the timed steps and the headline only (none of the secondary blocks); --dump-outputs writes the obs /
+    reward / done of the last timed step, and a second run with the same arguments writes the same arrays."""
+    import json, os, subprocess, sys
+    import numpy as np
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    dumps = []
+    for k in range(2):
+        d_out = str(tmp_path / f"run{k}")
+        out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "30", "--warmup", "5",
+                              "--dump-outputs", d_out], capture_output=True, text=True, timeout=600, cwd=root)
+        assert out.returncode == 0, out.stderr[-2000:]
+        lines = [l for l in out.stdout.splitlines() if l.strip().startswith("{")]
+        assert len(lines) == 1
+        d = json.loads(lines[0])
+        assert d["steps"] == 30 and d["warmup"] == 5 and d["finite"] and d["unit"] == "env-steps/s" and d["higher_is_better"]
+        assert abs(d["value"] - 4096 * 30 / (d["ms_per_step"] * 1e-3 * 30)) / d["value"] < 1e-9
+        assert d["roofline"]["kernel_ms_over"].startswith("30 of the 30 timed launches")
+        for key in ("segment_launch", "walking_gait_workload", "closed_loop", "cpu_baseline", "joint_rmse_vs_oracle", "vs_pybullet_record"):
+            assert key not in d, key
+        arrays = {name: np.load(os.path.join(d_out, name + ".npy")) for name in ("obs", "reward", "done")}
+        assert arrays["obs"].ndim == 2 and arrays["obs"].shape[0] == 4096 and arrays["reward"].shape == (4096,) and arrays["done"].shape == (4096,)
+        assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in arrays.values())
+        dumps.append(arrays)
+    for name in dumps[0]:
+        assert np.array_equal(dumps[0][name], dumps[1][name]), name
+
+
 def test_bench_two_ranks_gather_rollout_segments(torch):
     """The multi-GPU launch path of bench.py on a one-GPU box: two ranks (gloo, sharing the GPU) run a strong-scaling shard of
     BASELINE configs[2] each and all-gather their rollout segments every 25 steps (the design's one collective, SURVEY 8e);
@@ -793,7 +821,7 @@ def test_bench_two_ranks_gather_rollout_segments(torch):
     # the plain spelling the driver uses: bench.py starts its own two ranks (torch.distributed.run, rendezvous on 127.0.0.1)
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "50", "--warmup", "25",
-                          "--config", "3", "--envs-per-gpu", "1024", "--backend", "gloo", "--no-cpu-baseline"],
+                          "--config", "3", "--envs-per-gpu", "1024", "--backend", "gloo", "--no-cpu-baseline", "--full"],
                          capture_output=True, text=True, timeout=900, cwd=root, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.strip().startswith("{")]
@@ -815,7 +843,7 @@ def test_bench_two_ranks_report_the_north_star_workload_and_segment_launches(tor
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "50", "--warmup", "10", "--backend", "gloo",
-                          "--no-cpu-baseline"], capture_output=True, text=True, timeout=900, cwd=root, env=env)
+                          "--no-cpu-baseline", "--full"], capture_output=True, text=True, timeout=900, cwd=root, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.strip().startswith("{")]
     assert len(lines) == 1

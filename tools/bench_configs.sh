@@ -6,7 +6,7 @@ mkdir -p gpurun_out
 OUT=gpurun_out/${TAG}_bench_configs.jsonl
 : > $OUT
 STEPS=${2:-1000}
-run() { python bench.py --steps $STEPS --warmup 100 --no-cpu-baseline --no-walking-workload "$@" 2>> gpurun_out/${TAG}_bench.err | tail -1 >> $OUT; }
+run() { python bench.py --steps $STEPS --warmup 100 --no-cpu-baseline --no-walking-workload --full "$@" 2>> "${OUT%/*}/${TAG}_bench.err" | tail -1 >> $OUT; }
 run
 run --task gallop --signal ol --envs-per-gpu 8192
 run --task turn --terrain random

@@ -10,6 +10,7 @@ TAG=$1; shift
 cd $GRAFT_REPO_ROOT
 mkdir -p gpurun_out
 P=gpurun_out/${TAG}_progress.txt
+D=${P%/*}     # the output directory
 stamp() { echo "$(date +%s) $*" >> $P; }
 declare -A WL=( [walk4096]="" [walk262144]="--envs-per-gpu 262144" [arm4096]="--mark arm" [mixedarm2048]="--mixed --mark arm --envs-per-gpu 2048"
                 [gallop8192]="--task gallop --signal ol --envs-per-gpu 8192" [turnhf4096]="--task turn --terrain random" [poses4096]="--task poses"
@@ -22,10 +23,10 @@ for step in "$@"; do
     parity)       rm -f gpurun_out/parity_windows.jsonl
                   timeout 900 python -m pytest tests/test_gpu_parity.py -q -m gpu -k "every_kernel_variant or walk_ik_trajectory_rmse" > gpurun_out/${TAG}_parity_tests.txt 2>&1 ;;
     gputests)     timeout 1500 python -m pytest tests -q -m gpu > gpurun_out/${TAG}_gpu_tests.txt 2>&1 ;;
-    bench)        timeout 300 bash -c "python bench.py > gpurun_out/${TAG}_bench.json 2> gpurun_out/${TAG}_bench.err" ;;
+    bench)        timeout 300 bash -c "python bench.py --full > $D/${TAG}_bench.json 2> $D/${TAG}_bench.err" ;;
     bench_driver) timeout 180 bash -c "python bench.py --gpus 1 --steps 20 --warmup 5 > gpurun_out/${TAG}_bench_driver_cmd.json 2>> gpurun_out/${TAG}_bench.err" ;;
-    bench_2rank)  timeout 300 bash -c "python bench.py --gpus 2 --steps 200 --warmup 50 --config 3 --backend gloo --no-cpu-baseline > gpurun_out/${TAG}_bench_2rank_gloo_1gpu.json 2>> gpurun_out/${TAG}_bench.err" ;;
-    bench_2rank_ns) timeout 300 bash -c "python bench.py --gpus 2 --steps 50 --warmup 10 --backend gloo --no-cpu-baseline > gpurun_out/${TAG}_bench_2rank_north_star_gloo_1gpu.json 2>> gpurun_out/${TAG}_bench.err" ;;
+    bench_2rank)  timeout 300 bash -c "python bench.py --gpus 2 --steps 200 --warmup 50 --config 3 --backend gloo --no-cpu-baseline --full > $D/${TAG}_bench_2rank_gloo_1gpu.json 2>> $D/${TAG}_bench.err" ;;
+    bench_2rank_ns) timeout 300 bash -c "python bench.py --gpus 2 --steps 50 --warmup 10 --backend gloo --no-cpu-baseline --full > $D/${TAG}_bench_2rank_north_star_gloo_1gpu.json 2>> $D/${TAG}_bench.err" ;;
     bench_configs) timeout 2400 bash -c "bash tools/bench_configs.sh ${TAG} 600 > gpurun_out/${TAG}_bench_configs.txt 2>&1" ;;
     ab:*)         IFS=: read -r _ libs flags <<< "$step"
                   OUT=gpurun_out/${TAG}_ab.txt; echo "== bench.py --steps 600 --warmup 100 $flags" >> $OUT
@@ -43,7 +44,7 @@ for step in "$@"; do
                   done ;;
     ppo_standup)  timeout 600 python -m rex_gym_amd.agents.ppo --task standup --signal ol --envs 512 --iterations 12 --max-length 400 > gpurun_out/${TAG}_ppo_standup.txt 2>&1
                   timeout 600 python -m rex_gym_amd.agents.ppo --task standup --signal ol --envs 512 --iterations 12 --max-length 400 --loop steps > gpurun_out/${TAG}_ppo_standup_per_step_loop.txt 2>&1 ;;
-    bench_walk8192) timeout 400 bash -c "python bench.py --envs-per-gpu 8192 --no-cpu-baseline > gpurun_out/${TAG}_bench_walk8192.json 2>> gpurun_out/${TAG}_bench.err" ;;
+    bench_walk8192) timeout 400 bash -c "python bench.py --envs-per-gpu 8192 --no-cpu-baseline --full > $D/${TAG}_bench_walk8192.json 2>> $D/${TAG}_bench.err" ;;
     prof_policy:*) IFS=: read -r _ pn pt <<< "$step"; pn=${pn:-4096}; pt=${pt:-25}; export TMPDIR=/tmp
                   ( cd /tmp && timeout 300 rocprofv3 --kernel-trace --stats -d $GRAFT_REPO_ROOT/gpurun_out/${TAG}_polprof -- python $GRAFT_REPO_ROOT/tools/closed_loop_run.py --envs $pn --segment $pt --launches 40 > $GRAFT_REPO_ROOT/gpurun_out/${TAG}_prof_policy_${pn}_T${pt}.txt 2>/dev/null )
                   python tools/rocprof_stats.py $(find gpurun_out/${TAG}_polprof -name "*_results.db" | head -1) --window 30:70 --csv gpurun_out/${TAG}_kernel_stats_policy_${pn}_T${pt}.csv | head -5 >> gpurun_out/${TAG}_prof_policy_${pn}_T${pt}.txt
