@@ -397,6 +397,25 @@ REX_API int rex_mixed_slot_map(const RexConfig* cfg, int envs_per_wave, int32_t*
  * device buffer -- the key a batch created under REX_REGROUP=1 is regrouped into waves by (opt-in). */
 REX_API int rex_get_sweeps(RexSim* sim, int32_t* d_out, void* stream);
 
+/* Rendering (the reference's RexGymEnv.render(mode="rgb_array"), rex_gym_env.py:416-439): a camera that follows each env's
+ * base.  The picture shows the COLLISION geometry the simulator uses (link boxes, full toe cylinders, the arm's collision
+ * cylinders -- csrc/rex_render_gen.h), in the links' URDF material colours, over the z = 0 plane (a two-tone checker) and the
+ * env's heightfield; not the reference's visual meshes.  Bullet's b3ComputeViewMatrixFromYawPitchRoll convention, up axis z:
+ * eye = target + Rz(yaw) Rx(pitch) (0, -distance, 0), up = Rz(yaw) Rx(pitch) (0, 0, 1); perspective with a VERTICAL field of
+ * view fov_deg and aspect width / height.  Angles in degrees. */
+typedef struct RexCamera { float distance, yaw_deg, pitch_deg, fov_deg, near_plane, far_plane; } RexCamera;
+/* The reference's camera: distance 1.0, yaw 0, pitch -30 (rex_gym_env.py:214-216), fov 60, near 0.1, far 100. */
+REX_API int rex_default_camera(RexCamera* cam);
+/* Render n envs: output row k shows env d_env_ids[k] (int32 device array of state indices, which the caller keeps in
+ * [0, num_envs): they are not clamped).  d_rgb: uint8 [n][height][width][3], row 0 = the top of the image; d_depth (may be
+ * NULL): float32 [n][height][width], eye-space distance along the view axis [m], far_plane where nothing is hit; d_seg (may
+ * be NULL): int16 [n][height][width], -1 nothing, 0 ground, 1 + b body b (rex_model_gen.h numbering; arm bodies 13..18).
+ * One launch on `stream`, no host sync; reads the state, writes only the three buffers.  REX_EINVAL without a launch for
+ * n < 1, width or height outside 1..4096, n * width * height * 3 >= 2^31, a null d_rgb or d_env_ids, or a distance,
+ * fov or near plane that is not positive (or far_plane <= near_plane). */
+REX_API int rex_render(RexSim* sim, const RexCamera* cam, const int32_t* d_env_ids, int n, int width, int height,
+                       uint8_t* d_rgb, float* d_depth, int16_t* d_seg, void* stream);
+
 REX_API const char* rex_last_error(void);
 REX_API int rex_abi_version(void);
 

@@ -47,6 +47,12 @@ class RexPolicy(ctypes.Structure):
     ]
 
 
+class RexCamera(ctypes.Structure):
+    """Mirror of `struct RexCamera` (include/rexsim.h): the follow camera of rex_render (angles in degrees)."""
+    _fields_ = [("distance", ctypes.c_float), ("yaw_deg", ctypes.c_float), ("pitch_deg", ctypes.c_float),
+                ("fov_deg", ctypes.c_float), ("near_plane", ctypes.c_float), ("far_plane", ctypes.c_float)]
+
+
 class RexSimError(RuntimeError):
     pass
 
@@ -89,6 +95,9 @@ _SIGS = {
     "rex_mixed_slot_map": ([ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int], ctypes.c_int),
     "rex_get_sweeps": ([ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p], ctypes.c_int),
     "rex_step_times_ms": ([ctypes.c_void_p, ctypes.POINTER(ctypes.c_float), ctypes.c_int], ctypes.c_int),
+    "rex_default_camera": ([ctypes.POINTER(RexCamera)], ctypes.c_int),
+    "rex_render": ([ctypes.c_void_p, ctypes.POINTER(RexCamera), ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                    ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p], ctypes.c_int),
     "rex_last_error": ([], ctypes.c_char_p),
     "rex_abi_version": ([], ctypes.c_int),
 }

@@ -140,10 +140,11 @@ class SimplePPOPolicy:
 
 
 @torch.no_grad()
-def play(env, policy, max_steps=2500):
+def play(env, policy, max_steps=2500, frames=None, video_env=0):
     """PolicyPlayer.play (policy_player.py:44-56) on every env of the batch at once: one episode each, until done.
 
-    Returns per-env (sum of rewards, episode length, whether the env ended by itself before max_steps)."""
+    frames: a list that receives env `video_env`'s camera frame (RexBatchEnv.render, uint8 [360, 480, 3] device tensor)
+    after every step.  Returns per-env (sum of rewards, episode length, whether the env ended by itself before max_steps)."""
     observ = env.reset()
     n = observ.shape[0]
     total = torch.zeros(n, device=observ.device)
@@ -152,6 +153,8 @@ def play(env, policy, max_steps=2500):
     for _ in range(max_steps):
         action = policy.get_action(observ)
         observ, reward, done, _ = env.step(action)
+        if frames is not None:
+            frames.append(env.render("rgb_array", env_ids=[video_env])[0])
         total += torch.where(alive, reward.to(total.dtype), torch.zeros_like(total))
         length += alive.to(length.dtype)
         alive &= ~done.bool()
@@ -204,13 +207,24 @@ def main(argv=None):
     p.add_argument("--seed", type=int, default=0)
     p.add_argument("--fused", action="store_true", help="the actor inside the launch: one launch per --segment steps (play_segments)")
     p.add_argument("--segment", type=int, default=100)
+    p.add_argument("--video", metavar="PATH", help="write env --video-env's camera frames (one per step) as a GIF at 1 / control_time_step fps")
+    p.add_argument("--video-env", type=int, default=0)
     args = p.parse_args(argv)
+    if args.video and args.fused:
+        p.error("--video cannot go with --fused: a fused segment keeps no per-step state to draw")
+    if args.video and not 0 <= args.video_env < args.num_envs:
+        p.error("--video-env must lie in [0, --num-envs)")
     from ..envs import RexBatchEnv
     # (PolicyPlayer.play steps the bare env, policy_player.py:44-56: BatchEnv's per-step Box test -- a host sync per step here -- is not in that loop)
     env = RexBatchEnv(args.num_envs, task=args.env, signal_type=args.signal_type, seed=args.seed, check_actions=False,
                       range_normalize=args.fused, auto_reset=args.fused)
     policy = SimplePPOPolicy(env, args.checkpoint)
-    total, length, ended = play_segments(env, policy, args.max_steps, args.segment) if args.fused else play(env, policy, args.max_steps)
+    frames = [] if args.video else None
+    total, length, ended = (play_segments(env, policy, args.max_steps, args.segment) if args.fused
+                            else play(env, policy, args.max_steps, frames=frames, video_env=args.video_env))
+    if args.video:
+        from ..render import write_gif
+        write_gif(torch.stack(frames), args.video, 1.0 / env.control_time_step)
     x = env.state[0].float()
     print(json.dumps(dict(env=args.env, signal=args.signal_type, num_envs=args.num_envs,
                           mean_return=float(total.mean()), mean_length=float(length.float().mean()),

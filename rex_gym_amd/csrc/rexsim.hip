@@ -4,6 +4,7 @@
 // The step and settle kernels are instantiated in rex_step_*.hip / rex_settle.hip (rex_kernels.h); this file holds the
 // C ABI, the reset kernel and the small kernels (regrouping, controller-only entry points).
 #include "rex_kernels.h"
+#include "rex_render.h"
 #include <algorithm>
 #include <cstdarg>
 #include <vector>
@@ -883,6 +884,42 @@ int rex_last_step_ms(RexSim* s, float* ms) {
   if (!s->have_timing) return fail(REX_EINVAL, "rex_last_step_ms: no timed step recorded%s", "");
   HIPCHK(hipEventSynchronize(s->ev1));
   HIPCHK(hipEventElapsedTime(ms, s->ev0, s->ev1));
+  return REX_OK;
+}
+
+int rex_default_camera(RexCamera* cam) {
+  if (!cam) return fail(REX_EINVAL, "rex_default_camera: null pointer%s", "");
+  *cam = RexCamera{1.0f, 0.0f, -30.0f, 60.0f, 0.1f, 100.0f};   // rex_gym_env.py:214-216 and the projection of render(), :416-439
+  return REX_OK;
+}
+
+int rex_render(RexSim* s, const RexCamera* cam, const int32_t* d_env_ids, int n, int width, int height, uint8_t* d_rgb, float* d_depth,
+               int16_t* d_seg, void* stream) {
+  if (!s || !cam || !d_env_ids || !d_rgb) return fail(REX_EINVAL, "rex_render: null pointer%s", "");
+  if (n < 1 || width < 1 || width > 4096 || height < 1 || height > 4096 || (long long)n * width * height * 3 >= (1ll << 31))
+    return failf(REX_EINVAL, "rex_render: bad image batch (n %d, %d x %d: n >= 1, sides 1..4096, n * w * h * 3 < 2^31)", n, width, height);
+  if (!(cam->distance > 0.0f) || !(cam->fov_deg > 0.0f) || !(cam->fov_deg < 180.0f) || !(cam->near_plane > 0.0f) ||
+      !(cam->far_plane > cam->near_plane))
+    return fail(REX_EINVAL, "rex_render: camera distance, fov and near plane must be positive, fov < 180 and far > near%s", "");
+  // b3ComputeViewMatrixFromYawPitchRoll (up axis z): eye offset R (0, -d, 0), up R (0, 0, 1), R = Rz(yaw) Rx(pitch) (roll 0);
+  // then the look-at basis: forward = -offset / d, right = forward x up, up' = right x forward
+  const double deg = 3.14159265358979323846 / 180.0;
+  const double cy = cos(cam->yaw_deg * deg), sy = sin(cam->yaw_deg * deg), cp = cos(cam->pitch_deg * deg), sp = sin(cam->pitch_deg * deg);
+  const double d = cam->distance;
+  const double off[3] = {sy * cp * d, -cy * cp * d, -sp * d};            // Rz(yaw) Rx(pitch) (0, -d, 0)
+  const double upv[3] = {-sy * -sp, cy * -sp, cp};                       // Rz(yaw) Rx(pitch) (0, 0, 1)
+  const double f[3] = {-off[0] / d, -off[1] / d, -off[2] / d};
+  double r[3] = {f[1] * upv[2] - f[2] * upv[1], f[2] * upv[0] - f[0] * upv[2], f[0] * upv[1] - f[1] * upv[0]};
+  const double rn = sqrt(r[0] * r[0] + r[1] * r[1] + r[2] * r[2]);
+  r[0] /= rn; r[1] /= rn; r[2] /= rn;
+  const double u[3] = {r[1] * f[2] - r[2] * f[1], r[2] * f[0] - r[0] * f[2], r[0] * f[1] - r[1] * f[0]};
+  rex::RenderCam rc;
+  for (int k = 0; k < 3; ++k) { rc.off[k] = (float)off[k]; rc.fwd[k] = (float)f[k]; rc.right[k] = (float)r[k]; rc.up[k] = (float)u[k]; }
+  const double ty = tan(0.5 * cam->fov_deg * deg);
+  rc.tan_y = (float)ty; rc.tan_x = (float)(ty * (double)width / (double)height);
+  rc.near_plane = cam->near_plane; rc.far_plane = cam->far_plane;
+  HIPCHK(hipSetDevice(s->device));
+  HIPCHK(rex_launch_render(s, rc, d_env_ids, n, width, height, d_rgb, d_depth, d_seg, (hipStream_t)stream));
   return REX_OK;
 }
 

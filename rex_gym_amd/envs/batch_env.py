@@ -67,7 +67,7 @@ class StepOut:
 
 
 class RexBatchEnv:
-    metadata = {"render.modes": []}
+    metadata = {"render.modes": ["rgb_array"]}
 
     def __init__(self, num_envs, task="walk", signal_type="ik", device=0, seed=0, env_index_base=0,
                  auto_reset=False, max_episode_steps=0, backwards=None, target_position=None,
@@ -405,6 +405,59 @@ class RexBatchEnv:
             out = self.bind_out(*out)
         _lib.check(self._L.rex_step(self._h, a.data_ptr(), out.p_obs, out.p_reward, out.p_done, self._p_cmd, self._stream_ptr()), "rex_step")
         return out.obs, out.reward, out.done_bool, self._info
+
+    def render(self, mode="rgb_array", env_ids=None, width=480, height=360, camera=None, depth=False, segmentation=False):
+        """Camera images of the batch (rex_render): the reference's RexGymEnv.render(mode="rgb_array") (rex_gym_env.py:416-439)
+        for many envs in one launch, on the env's stream, with no host sync.  The picture shows the collision geometry the
+        simulator uses (link boxes, full toe cylinders, the arm's collision cylinders), not the reference's meshes.
+
+        env_ids: the envs to draw (default all), row k of the result is env env_ids[k].  camera: a dict (or _lib.RexCamera)
+        with any of distance, yaw_deg, pitch_deg, fov_deg, near_plane, far_plane; the rest from the reference's camera
+        (1.0, 0, -30, 60, 0.1, 100).  Returns uint8 [k, height, width, 3] (row 0 = the top of the image); with depth or
+        segmentation, (rgb, {"depth": float32 [k, H, W] eye-space metres, far where nothing is hit, "segmentation": int16
+        [k, H, W] -1 nothing, 0 ground, 1 + b body b}) -- the entry not asked for is None."""
+        torch = self._torch
+        if mode != "rgb_array":
+            raise NotImplementedError(f"render mode {mode!r}: RexBatchEnv renders 'rgb_array' only (no GUI)")
+        cam = self._camera(camera)
+        width, height = int(width), int(height)
+        if not (1 <= width <= 4096 and 1 <= height <= 4096):
+            raise ValueError(f"render: width and height must lie in 1..4096, got {width} x {height}")
+        if not (cam.distance > 0 and 0 < cam.fov_deg < 180 and cam.near_plane > 0 and cam.far_plane > cam.near_plane):
+            raise ValueError("render: camera distance, fov and near plane must be positive (fov < 180, far > near)")
+        with self._on_stream():
+            if env_ids is None:
+                if getattr(self, "_all_ids", None) is None:
+                    self._all_ids = torch.arange(self.num_envs, dtype=torch.int32, device=self.device)
+                ids = self._all_ids
+            else:
+                host = np.asarray(env_ids.cpu() if hasattr(env_ids, "cpu") else env_ids, dtype=np.int64).reshape(-1)
+                if host.size == 0 or host.min() < 0 or host.max() >= self.num_envs:
+                    raise IndexError(f"render: env_ids must be non-empty and lie in [0, {self.num_envs})")
+                ids = torch.as_tensor(host.astype(np.int32), device=self.device)
+            k = int(ids.numel())
+            if k * width * height * 3 >= 2 ** 31:
+                raise ValueError("render: k * width * height * 3 must stay below 2^31 bytes")
+            rgb = torch.empty((k, height, width, 3), dtype=torch.uint8, device=self.device)
+            dep = torch.empty((k, height, width), dtype=torch.float32, device=self.device) if depth else None
+            seg = torch.empty((k, height, width), dtype=torch.int16, device=self.device) if segmentation else None
+            _lib.check(self._L.rex_render(self._h, ctypes.byref(cam), ids.data_ptr(), k, width, height, rgb.data_ptr(),
+                                          dep.data_ptr() if dep is not None else None, seg.data_ptr() if seg is not None else None,
+                                          self._stream_ptr()), "rex_render")
+        if depth or segmentation:
+            return rgb, {"depth": dep, "segmentation": seg}
+        return rgb
+
+    def _camera(self, camera):
+        if isinstance(camera, _lib.RexCamera):
+            return camera
+        cam = _lib.RexCamera()
+        _lib.check(self._L.rex_default_camera(ctypes.byref(cam)), "rex_default_camera")
+        for key, v in (camera or {}).items():
+            if key not in ("distance", "yaw_deg", "pitch_deg", "fov_deg", "near_plane", "far_plane"):
+                raise TypeError(f"render: unknown camera field {key!r}")
+            setattr(cam, key, float(v))
+        return cam
 
     def _action_bounds(self):
         if self._act_lo is None:

@@ -28,6 +28,8 @@ class _SingleEnv:
         self.rex = self._batch.rex     # what an env_randomizer's randomize_env(env) reaches for (envs/rex_knobs.py)
         # the hooks get THIS env object, as in the reference (rex_gym_env.py:345-346)
         self._batch._env_randomizers = [_Forward(r, self) for r in self._batch._env_randomizers]
+        # the reference's follow camera (rex_gym_env.py:214-216); render() reads these attributes on every call
+        self._cam_dist, self._cam_yaw, self._cam_pitch = 1.0, 0, -30
 
     def add_env_randomizer(self, env_randomizer):
         self._batch.add_env_randomizer(_Forward(env_randomizer, self))
@@ -46,7 +48,14 @@ class _SingleEnv:
                 {"action": info["action"][0].cpu().numpy().astype(np.float64)})
 
     def render(self, mode="rgb_array", close=False):
-        return np.array([])
+        """mode 'rgb_array': a uint8 (360, 480, 3) frame of the follow camera (rex_gym_env.py:416-439), drawn by the HIP
+        renderer from the collision geometry; any other mode (the GUI's 'human') returns an empty array, as the reference
+        does outside rgb_array."""
+        if mode != "rgb_array":
+            return np.array([])
+        rgb = self._batch.render("rgb_array", width=480, height=360,
+                                 camera={"distance": self._cam_dist, "yaw_deg": self._cam_yaw, "pitch_deg": self._cam_pitch})
+        return rgb[0].cpu().numpy()
 
     def close(self):
         self._batch.close()

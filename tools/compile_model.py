@@ -19,6 +19,9 @@ What it reproduces (marked UNVERIFIED against a live PyBull
   * the toe collision hull (half cylinder, stl/foot.stl) is reduced to an
     analytic cylinder segment about the toe-link y axis.
 
+With the reference's rex_arm.urdf present it also writes rex_arm_model_gen.h (the 6 arm bodies of mark 'arm') and
+rex_render_gen.h (the primitives the renderer draws: collision boxes and cylinders with the links' material colours).
+
 Usage: python tools/compile_model.py [--urdf PATH] [--out PATH]
 """
 import argparse
@@ -311,6 +314,119 @@ def emit_arm(base_bodies):
         print(13 + i, b["name"], "parent", b["parent"], "m=%.3f" % b["mass"], "com", np.round(b["com"], 5), "I", np.round(b["I"], 7).tolist())
 
 
+DEFAULT_RENDER_OUT = os.path.join(os.path.dirname(DEFAULT_OUT), "rex_render_gen.h")
+
+
+def link_colours(urdf):
+    """link name -> RGB of the <material> of the link's first <visual> (named materials resolved at the top of the file)."""
+    root = ET.parse(urdf).getroot()
+    named = {}
+    for m in root.findall("material"):
+        c = m.find("color")
+        if c is not None:
+            named[m.get("name")] = [float(v) for v in c.get("rgba").split()][:3]
+    out = {}
+    for l in root.findall("link"):
+        v = l.find("visual")
+        m = v.find("material") if v is not None else None
+        if m is None:
+            continue
+        c = m.find("color")
+        out[l.get("name")] = [float(v) for v in c.get("rgba").split()][:3] if c is not None else named[m.get("name")]
+    return out
+
+
+def frame_from_axis(a):
+    """Rotation whose third column is the unit vector a (a cylinder's axis is its local z)."""
+    a = np.asarray(a, dtype=np.float64) / np.linalg.norm(a)
+    t = np.array([1.0, 0.0, 0.0]) if abs(a[0]) < 0.9 else np.array([0.0, 1.0, 0.0])
+    x = np.cross(t, a)
+    x /= np.linalg.norm(x)
+    return np.stack([x, np.cross(a, x), a], axis=1)
+
+
+def emit_render():
+    """rex_render_gen.h: the primitives the renderer draws (csrc/rex_render.hip) -- the collision geometry, not the visual meshes.
+    Mark 'base' = the REX_BOX_* boxes and the REX_TOE_* cylinders exactly as the physics uses them; mark 'arm' adds the
+    collision cylinders of the six arm links (drawn only: the physics does not collide them).  Colour = the link's visual
+    material; a merged fixed link keeps its own."""
+    bodies, links = load_bodies(DEFAULT_URDF, BASE_MOTOR_NAMES)
+    colour = link_colours(DEFAULT_URDF)
+    prims = []   # (kind, body, pos, R, ext, rgb, link)
+    toes = []
+    for bi, b in enumerate(bodies):
+        for ln, xyz, R in sorted(b["members"], key=lambda m: m[0] != b["name"]):
+            for kind, prm, cx, crpy in links[ln].collisions:
+                if kind == "box":    # same walk as the REX_BOX_* table of rex_model_gen.h
+                    prims.append((0, bi, xyz + cx, np.eye(3), np.asarray(prm) / 2.0, colour[ln], ln))
+                elif kind == "mesh":   # the toe hull as the physics sees it: the full cylinder segment about the hull's y axis
+                    Rc = rpy_to_mat(crpy)
+                    rad = float(np.sqrt(prm[:, 0] ** 2 + prm[:, 2] ** 2).max())
+                    ymin, ymax = prm[:, 1].min(), prm[:, 1].max()
+                    ctr = xyz + R @ (Rc @ np.array([0.0, 0.5 * (ymin + ymax), 0.0]) + cx)
+                    axis = R @ Rc @ np.array([0.0, 1.0, 0.0])
+                    toes.append((1, bi, ctr, frame_from_axis(axis), np.array([rad, rad, 0.5 * (ymax - ymin)]), colour[ln], ln))
+    toes.sort(key=lambda t: t[1])
+    assert len(prims) == 15 and len(toes) == 4
+    prims += toes
+    n_base = len(prims)
+    abodies, alinks = load_bodies(DEFAULT_ARM_URDF, BASE_MOTOR_NAMES + ARM_MOTOR_NAMES)
+    acolour = link_colours(DEFAULT_ARM_URDF)
+    aroot = ET.parse(DEFAULT_ARM_URDF).getroot()
+    for bi in range(13, len(abodies)):
+        b = abodies[bi]
+        for ln, xyz, R in sorted(b["members"], key=lambda m: m[0] != b["name"]):
+            elem = [l for l in aroot.findall("link") if l.get("name") == ln][0]
+            for c in elem.findall("collision"):
+                cyl = c.find("geometry").find("cylinder")   # (arm_section_4 also lists a box in the same <geometry>: the cylinder is drawn)
+                if cyl is None:
+                    continue
+                cxyz, crpy = parse_origin(c)
+                prims.append((1, bi, xyz + R @ cxyz, R @ rpy_to_mat(crpy),
+                              np.array([float(cyl.get("radius")), float(cyl.get("radius")), 0.5 * float(cyl.get("length"))]),
+                              acolour[ln], ln))
+    assert len(prims) == n_base + 6
+    out = []
+    w = out.append
+    w("// GENERATED by tools/compile_model.py from the reference's rex.urdf / rex_arm.urdf -- do not edit.")
+    w("// The primitives the renderer draws (csrc/rex_render.hip): the COLLISION geometry, not the visual meshes.  Entries")
+    w("// 0..REX_RENDER_NPRIM_BASE-1 are mark 'base': the REX_BOX_* boxes and the full REX_TOE_* cylinders of rex_model_gen.h; mark")
+    w("// 'arm' draws all REX_RENDER_NPRIM_ARM: in addition the collision cylinders of the six arm links (the physics does not")
+    w("// collide them).  Pose in the frame of body REX_RENDER_BODY (numbered as in rex_model_gen.h, arm bodies 13..18):")
+    w("// centre, and rotation whose columns are the primitive's local axes (row-major).  Extents: box = half extents along")
+    w("// the local axes; cylinder = radius, radius, half length along the local z.  Colour = the <material> of the link's")
+    w("// <visual> (rex.urdf:3-11); a merged fixed link keeps its own.")
+    w("#ifndef REX_RENDER_GEN_H")
+    w("#define REX_RENDER_GEN_H")
+    w('#include "rex_model_gen.h"')
+    w("#define REX_RENDER_BOX 0")
+    w("#define REX_RENDER_CYL 1")
+    w(f"#define REX_RENDER_NPRIM_BASE {n_base}")
+    w(f"#define REX_RENDER_NPRIM_ARM {len(prims)}")
+    w("REX_CONST int REX_RENDER_KIND[REX_RENDER_NPRIM_ARM] = {" + ", ".join(str(p[0]) for p in prims) + "};")
+    w("REX_CONST int REX_RENDER_BODY[REX_RENDER_NPRIM_ARM] = {" + ", ".join(str(p[1]) for p in prims) + "};")
+    w("REX_CONST double REX_RENDER_POS[REX_RENDER_NPRIM_ARM][3] = {")
+    for p in prims:
+        w("  {" + ", ".join(fmt(v) for v in p[2]) + "},  /* " + p[6] + " */")
+    w("};")
+    w("REX_CONST double REX_RENDER_ROT[REX_RENDER_NPRIM_ARM][9] = {")
+    for p in prims:
+        w("  {" + ", ".join(fmt(v) for v in np.asarray(p[3]).ravel()) + "},")
+    w("};")
+    w("REX_CONST double REX_RENDER_EXT[REX_RENDER_NPRIM_ARM][3] = {")
+    for p in prims:
+        w("  {" + ", ".join(fmt(v) for v in p[4]) + "},")
+    w("};")
+    w("REX_CONST double REX_RENDER_RGB[REX_RENDER_NPRIM_ARM][3] = {")
+    for p in prims:
+        w("  {" + ", ".join(fmt(v) for v in p[5]) + "},")
+    w("};")
+    w("#endif /* REX_RENDER_GEN_H */")
+    with open(DEFAULT_RENDER_OUT, "w") as f:
+        f.write("\n".join(out) + "\n")
+    print(f"wrote {DEFAULT_RENDER_OUT}: {n_base} + {len(prims) - n_base} primitives")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--urdf", default=DEFAULT_URDF)
@@ -523,3 +639,4 @@ if __name__ == "__main__":
     main()
     if os.path.exists(DEFAULT_ARM_URDF):
         emit_arm(load_bodies(DEFAULT_URDF, BASE_MOTOR_NAMES)[0])
+        emit_render()
