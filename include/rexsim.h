@@ -398,9 +398,9 @@ REX_API int rex_mixed_slot_map(const RexConfig* cfg, int envs_per_wave, int32_t*
 REX_API int rex_get_sweeps(RexSim* sim, int32_t* d_out, void* stream);
 
 /* Rendering (the reference's RexGymEnv.render(mode="rgb_array"), rex_gym_env.py:416-439): a camera that follows each env's
- * base.  The picture shows the COLLISION geometry the simulator uses (link boxes, full toe cylinders, the arm's collision
- * cylinders -- csrc/rex_render_gen.h), in the links' URDF material colours, over the z = 0 plane (a two-tone checker) and the
- * env's heightfield; not the reference's visual meshes.  Bullet's b3ComputeViewMatrixFromYawPitchRoll convention, up axis z:
+ * base.  rex_render's picture shows the COLLISION geometry the simulator uses (link boxes, full toe cylinders, the arm's
+ * collision cylinders -- csrc/rex_render_gen.h), in the links' URDF material colours, over the z = 0 plane (a two-tone checker)
+ * and the env's heightfield.  rex_render_visual draws the URDF's visual meshes instead (opt-in: rex_render_set_visuals).  Bullet's b3ComputeViewMatrixFromYawPitchRoll convention, up axis z:
  * eye = target + Rz(yaw) Rx(pitch) (0, -distance, 0), up = Rz(yaw) Rx(pitch) (0, 0, 1); perspective with a VERTICAL field of
  * view fov_deg and aspect width / height.  Angles in degrees. */
 typedef struct RexCamera { float distance, yaw_deg, pitch_deg, fov_deg, near_plane, far_plane; } RexCamera;
@@ -415,6 +415,20 @@ REX_API int rex_default_camera(RexCamera* cam);
  * fov or near plane that is not positive (or far_plane <= near_plane). */
 REX_API int rex_render(RexSim* sim, const RexCamera* cam, const int32_t* d_env_ids, int n, int width, int height,
                        uint8_t* d_rgb, float* d_depth, int16_t* d_seg, void* stream);
+/* The visual meshes of the sim's mark (csrc/rex_visual_gen.h: 23 instances for 'base', 29 for 'arm'), as BVHs built on the
+ * host (rex_gym_amd/meshes.py).  Host arrays: nodes [num_nodes][16] dwords (float lo0[3] hi0[3] lo1[3] hi1[3] = both children's
+ * boxes, int32 c0 c1, 2 unused; c >= 0 an inner node whose index is greater than its parent's, c < 0 a leaf with
+ * ~c = first triangle << 3 | (count - 1)); tris [num_tris][9] floats (v0, v1 - v0, v2 - v0) in metres, in the instance's mesh
+ * frame; inst_root [num_inst] (a root node, or -1 for an empty mesh) and inst_box [num_inst][6] (the root's mesh-frame box lo,
+ * hi).  REX_EINVAL (message in rex_last_error) for a wrong instance count, out-of-range children or triangles, a node with
+ * two parents, or a tree deeper than 32 levels.  Uploads on `stream` and waits for the copy; the sim keeps the device copy
+ * (replacing an earlier one) until rex_destroy. */
+REX_API int rex_render_set_visuals(RexSim* sim, const float* nodes, int num_nodes, const float* tris, int num_tris,
+                                   const int32_t* inst_root, const float* inst_box, int num_inst, void* stream);
+/* rex_render over the visual meshes: same arguments, outputs and checks, and the same labels (segment 1 + b for every mesh
+ * riding on body b).  REX_EINVAL without a launch when no visuals are set. */
+REX_API int rex_render_visual(RexSim* sim, const RexCamera* cam, const int32_t* d_env_ids, int n, int width, int height,
+                              uint8_t* d_rgb, float* d_depth, int16_t* d_seg, void* stream);
 
 REX_API const char* rex_last_error(void);
 REX_API int rex_abi_version(void);

@@ -98,6 +98,10 @@ _SIGS = {
     "rex_default_camera": ([ctypes.POINTER(RexCamera)], ctypes.c_int),
     "rex_render": ([ctypes.c_void_p, ctypes.POINTER(RexCamera), ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                     ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p], ctypes.c_int),
+    "rex_render_set_visuals": ([ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
+                                ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p], ctypes.c_int),
+    "rex_render_visual": ([ctypes.c_void_p, ctypes.POINTER(RexCamera), ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                           ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p], ctypes.c_int),
     "rex_last_error": ([], ctypes.c_char_p),
     "rex_abi_version": ([], ctypes.c_int),
 }

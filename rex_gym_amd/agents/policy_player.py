@@ -209,16 +209,23 @@ def main(argv=None):
     p.add_argument("--segment", type=int, default=100)
     p.add_argument("--video", metavar="PATH", help="write env --video-env's camera frames (one per step) as a GIF at 1 / control_time_step fps")
     p.add_argument("--video-env", type=int, default=0)
+    p.add_argument("--video-meshes", metavar="DATA_PATH", nargs="?", const="", default=None,
+                   help="draw the --video frames from the URDF's visual meshes read under DATA_PATH "
+                        "(rex_gym.util.pybullet_data.getDataPath(); default: that of an installed rex_gym)")
     args = p.parse_args(argv)
     if args.video and args.fused:
         p.error("--video cannot go with --fused: a fused segment keeps no per-step state to draw")
     if args.video and not 0 <= args.video_env < args.num_envs:
         p.error("--video-env must lie in [0, --num-envs)")
+    if args.video_meshes is not None and not args.video:
+        p.error("--video-meshes goes with --video")
     from ..envs import RexBatchEnv
     # (PolicyPlayer.play steps the bare env, policy_player.py:44-56: BatchEnv's per-step Box test -- a host sync per step here -- is not in that loop)
     env = RexBatchEnv(args.num_envs, task=args.env, signal_type=args.signal_type, seed=args.seed, check_actions=False,
                       range_normalize=args.fused, auto_reset=args.fused)
     policy = SimplePPOPolicy(env, args.checkpoint)
+    if args.video_meshes is not None:
+        env.load_visual_meshes(args.video_meshes or None)
     frames = [] if args.video else None
     total, length, ended = (play_segments(env, policy, args.max_steps, args.segment) if args.fused
                             else play(env, policy, args.max_steps, frames=frames, video_env=args.video_env))

@@ -23,7 +23,7 @@ LIB_PATH = os.environ.get("REX_LIB_PATH") or os.path.join(PKG_DIR, "librexsim_hi
 # translation unit -> variant group name (REX_BUILD_ONLY) ; rexsim.hip (C ABI, reset and controller kernels) is always built
 GROUPS = {"rex_step_base.hip": "base", "rex_step_arm.hip": "arm", "rex_step_mixed_base.hip": "mixed_base",
           "rex_step_mixed_arm.hip": "mixed_arm", "rex_step_body.hip": "body", "rex_settle_base.hip": "base", "rex_settle_arm.hip": "arm"}
-SOURCES = ["rexsim.hip", "rex_render.hip"] + sorted(GROUPS)   # rex_render.hip: the renderer (rex_render), one kernel, no variants
+SOURCES = ["rexsim.hip", "rex_render.hip", "rex_render_mesh.hip"] + sorted(GROUPS)   # the renderers (rex_render, rex_render_visual): one kernel each, no variants
 # the step translation units are compiled a second time with -DREX_TU_TRACE=1: the kernel instantiations with the event trace
 # (rex_set_event_trace, a debug aid of the parity tests) compiled in -- the product kernels carry none of it
 TRACE_SOURCES = sorted(f for f in GROUPS if f.startswith("rex_step_"))

@@ -1319,6 +1319,13 @@ struct RexSim {
   bool use_policy;        // this launch runs the fused-actor kernels (set by step_launch)
   int pol_attr_bytes;     // the dynamic-LDS limit this sim has already set on its fused-actor kernel (hipFuncSetAttribute)
   int pol_lds_bytes;      // dynamic LDS of the fused-actor kernels: the weights' copy (0: they do not fit next to four waves' rows and are streamed)
+  // rex_render_set_visuals: one device allocation holding the BVH nodes [16 dwords each], the leaf-ordered triangles [9 floats],
+  // and per visual instance its root node and mesh-frame root box [6 floats] (rex_render_mesh.hip); null until set
+  void* d_vis;
+  float* d_vis_nodes;
+  float* d_vis_tris;
+  int32_t* d_vis_root;
+  float* d_vis_box;
 };
 
 // launchers, one per variant group (each in its own translation unit)

@@ -1,7 +1,9 @@
-// rex_render.h -- batched ray-cast renderer of the simulated scene (rex_render): what the camera of the reference's
-// RexGymEnv.render(mode="rgb_array") (rex_gym_env.py:416-439) would see, drawn from the COLLISION geometry the simulator
-// uses (rex_render_gen.h: link boxes, full toe cylinders, the arm's cylinders) over the ground plane / the env's heightfield.
-// A separate, read-only launch: it reads the caller-owned state and the terrain pool, and writes the caller's image buffers only.
+// rex_render.h -- batched ray-cast renderer of the simulated scene: what the camera of the reference's
+// RexGymEnv.render(mode="rgb_array") (rex_gym_env.py:416-439) would see, over the ground plane / the env's heightfield.
+// rex_render draws the COLLISION geometry the simulator uses (rex_render_gen.h: link boxes, full toe cylinders, the arm's
+// cylinders); rex_render_visual draws the URDF's visual meshes (rex_visual_gen.h, BVHs set by rex_render_set_visuals).
+// Separate, read-only launches: they read the caller-owned state, the terrain pool and the visual buffers, and write the
+// caller's image buffers only.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -32,6 +34,10 @@ constexpr float kSkyR = 0.70f, kSkyG = 0.80f, kSkyB = 0.92f;
 constexpr float kCheckerAR = 0.25f, kCheckerAG = 0.40f, kCheckerAB = 0.65f;
 constexpr float kCheckerBR = 0.85f, kCheckerBG = 0.88f, kCheckerBB = 0.92f;
 
+// The mesh kernel's per-thread BVH traversal stack (LDS, 256 threads x 32 entries x 4 B = 32 KiB): rex_render_set_visuals
+// refuses trees with more than kMeshStack levels of inner nodes, so a traversal never holds more entries.
+constexpr int kMeshStack = 32;
+
 }  // namespace rex
 
 // Launch one rex_render_kernel over n envs (d_ids[k] = the state's env index of output row k): grid (n, pixel tiles of
@@ -39,3 +45,6 @@ constexpr float kCheckerBR = 0.85f, kCheckerBG = 0.88f, kCheckerBB = 0.92f;
 // by the caller (rex_render in rexsim.hip).
 hipError_t rex_launch_render(const RexSim* s, const rex::RenderCam& cam, const int32_t* d_ids, int n, int width, int height,
                              uint8_t* d_rgb, float* d_depth, int16_t* d_seg, hipStream_t st);
+// The same over the visual meshes (rex_render_mesh.hip): the BVH buffers of rex_render_set_visuals, already validated.
+hipError_t rex_launch_render_mesh(const RexSim* s, const rex::RenderCam& cam, const int32_t* d_ids, int n, int width, int height,
+                                  uint8_t* d_rgb, float* d_depth, int16_t* d_seg, hipStream_t st);

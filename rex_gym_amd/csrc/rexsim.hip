@@ -5,8 +5,10 @@
 // C ABI, the reset kernel and the small kernels (regrouping, controller-only entry points).
 #include "rex_kernels.h"
 #include "rex_render.h"
+#include "rex_visual_gen.h"
 #include <algorithm>
 #include <cstdarg>
+#include <cstring>
 #include <vector>
 
 namespace rex {
@@ -642,6 +644,7 @@ int rex_destroy(RexSim* s) {
   if (s->d_block_task) (void)hipFree(s->d_block_task);
   if (s->d_class) (void)hipFree(s->d_class);
   if (s->d_polbuf) (void)hipFree(s->d_polbuf);
+  if (s->d_vis) (void)hipFree(s->d_vis);
   if (s->ev0) (void)hipEventDestroy(s->ev0);
   if (s->ev1) (void)hipEventDestroy(s->ev1);
   for (int k = 0; k < REX_TIMING_RING; ++k) if (s->ring0[k]) { (void)hipEventDestroy(s->ring0[k]); (void)hipEventDestroy(s->ring1[k]); }
@@ -893,14 +896,15 @@ int rex_default_camera(RexCamera* cam) {
   return REX_OK;
 }
 
-int rex_render(RexSim* s, const RexCamera* cam, const int32_t* d_env_ids, int n, int width, int height, uint8_t* d_rgb, float* d_depth,
-               int16_t* d_seg, void* stream) {
-  if (!s || !cam || !d_env_ids || !d_rgb) return fail(REX_EINVAL, "rex_render: null pointer%s", "");
+// the checks rex_render and rex_render_visual share, and the camera of the launch in world axes
+static int render_camera(const char* who, RexSim* s, const RexCamera* cam, const int32_t* d_env_ids, int n, int width, int height,
+                         uint8_t* d_rgb, rex::RenderCam& rc) {
+  if (!s || !cam || !d_env_ids || !d_rgb) return failf(REX_EINVAL, "%s: null pointer", who);
   if (n < 1 || width < 1 || width > 4096 || height < 1 || height > 4096 || (long long)n * width * height * 3 >= (1ll << 31))
-    return failf(REX_EINVAL, "rex_render: bad image batch (n %d, %d x %d: n >= 1, sides 1..4096, n * w * h * 3 < 2^31)", n, width, height);
+    return failf(REX_EINVAL, "%s: bad image batch (n %d, %d x %d: n >= 1, sides 1..4096, n * w * h * 3 < 2^31)", who, n, width, height);
   if (!(cam->distance > 0.0f) || !(cam->fov_deg > 0.0f) || !(cam->fov_deg < 180.0f) || !(cam->near_plane > 0.0f) ||
       !(cam->far_plane > cam->near_plane))
-    return fail(REX_EINVAL, "rex_render: camera distance, fov and near plane must be positive, fov < 180 and far > near%s", "");
+    return failf(REX_EINVAL, "%s: camera distance, fov and near plane must be positive, fov < 180 and far > near", who);
   // b3ComputeViewMatrixFromYawPitchRoll (up axis z): eye offset R (0, -d, 0), up R (0, 0, 1), R = Rz(yaw) Rx(pitch) (roll 0);
   // then the look-at basis: forward = -offset / d, right = forward x up, up' = right x forward
   const double deg = 3.14159265358979323846 / 180.0;
@@ -913,13 +917,92 @@ int rex_render(RexSim* s, const RexCamera* cam, const int32_t* d_env_ids, int n,
   const double rn = sqrt(r[0] * r[0] + r[1] * r[1] + r[2] * r[2]);
   r[0] /= rn; r[1] /= rn; r[2] /= rn;
   const double u[3] = {r[1] * f[2] - r[2] * f[1], r[2] * f[0] - r[0] * f[2], r[0] * f[1] - r[1] * f[0]};
-  rex::RenderCam rc;
   for (int k = 0; k < 3; ++k) { rc.off[k] = (float)off[k]; rc.fwd[k] = (float)f[k]; rc.right[k] = (float)r[k]; rc.up[k] = (float)u[k]; }
   const double ty = tan(0.5 * cam->fov_deg * deg);
   rc.tan_y = (float)ty; rc.tan_x = (float)(ty * (double)width / (double)height);
   rc.near_plane = cam->near_plane; rc.far_plane = cam->far_plane;
+  return REX_OK;
+}
+
+int rex_render(RexSim* s, const RexCamera* cam, const int32_t* d_env_ids, int n, int width, int height, uint8_t* d_rgb, float* d_depth,
+               int16_t* d_seg, void* stream) {
+  rex::RenderCam rc;
+  const int rc_err = render_camera("rex_render", s, cam, d_env_ids, n, width, height, d_rgb, rc);
+  if (rc_err != REX_OK) return rc_err;
   HIPCHK(hipSetDevice(s->device));
   HIPCHK(rex_launch_render(s, rc, d_env_ids, n, width, height, d_rgb, d_depth, d_seg, (hipStream_t)stream));
+  return REX_OK;
+}
+
+int rex_render_set_visuals(RexSim* s, const float* nodes, int num_nodes, const float* tris, int num_tris, const int32_t* inst_root,
+                           const float* inst_box, int num_inst, void* stream) {
+  if (!s || !inst_root || !inst_box || (num_nodes > 0 && !nodes) || (num_tris > 0 && !tris))
+    return fail(REX_EINVAL, "rex_render_set_visuals: null pointer%s", "");
+  const int want = s->cfg.mark == REX_MARK_ARM ? REX_VIS_N_ARM : REX_VIS_N_BASE;
+  if (num_inst != want) return failf(REX_EINVAL, "rex_render_set_visuals: %d instances, this sim's mark draws %d", num_inst, want);
+  if (num_nodes < 0 || num_tris < 0 || num_nodes >= (1 << 26) || num_tris >= (1 << 26))
+    return failf(REX_EINVAL, "rex_render_set_visuals: bad counts (%d nodes, %d triangles: 0 .. 2^26)", num_nodes, num_tris);
+  // every child index points forward (so the tree is acyclic), every leaf's triangles exist, and no root reaches deeper than
+  // kMeshStack levels of inner nodes (the kernel's traversal stack)
+  std::vector<int> depth(num_nodes, 0), parents(num_nodes, 0);
+  for (int i = 0; i < num_nodes; ++i)
+    for (int c = 0; c < 2; ++c) {
+      int32_t ch;
+      memcpy(&ch, nodes + 16 * (size_t)i + 12 + c, 4);
+      if (ch >= 0) {
+        if (ch <= i || ch >= num_nodes) return failf(REX_EINVAL, "rex_render_set_visuals: node %d: child %d out of range", i, ch);
+        ++parents[ch];
+      } else {
+        const long long start = (long long)(~ch >> 3), cnt = (~ch & 7) + 1;
+        if (start + cnt > num_tris) return failf(REX_EINVAL, "rex_render_set_visuals: node %d: leaf triangles %lld..%lld out of range", i, start, start + cnt);
+      }
+    }
+  for (int i = 0; i < num_nodes; ++i) {
+    if (parents[i] > 1) return failf(REX_EINVAL, "rex_render_set_visuals: node %d has %d parents", i, parents[i]);
+    if (parents[i] == 0) depth[i] = 1;
+    if (depth[i] > rex::kMeshStack) return failf(REX_EINVAL, "rex_render_set_visuals: a tree deeper than %d levels", rex::kMeshStack);
+    for (int c = 0; c < 2; ++c) {
+      int32_t ch;
+      memcpy(&ch, nodes + 16 * (size_t)i + 12 + c, 4);
+      if (ch >= 0) depth[ch] = depth[i] + 1;
+    }
+  }
+  for (int k = 0; k < num_inst; ++k) {
+    if (inst_root[k] < -1 || inst_root[k] >= num_nodes || (inst_root[k] >= 0 && parents[inst_root[k]] != 0))
+      return failf(REX_EINVAL, "rex_render_set_visuals: instance %d: root %d is not a root node", k, inst_root[k]);
+  }
+  HIPCHK(hipSetDevice(s->device));
+  const size_t b_nodes = 64 * (size_t)num_nodes, b_tris = 36 * (size_t)num_tris, b_root = 4 * (size_t)num_inst;
+  const size_t o_tris = b_nodes, o_root = (o_tris + b_tris + 15) & ~(size_t)15, o_box = o_root + ((b_root + 15) & ~(size_t)15);
+  const size_t total = o_box + 24 * (size_t)num_inst;
+  void* buf = nullptr;
+  hipError_t e = hipMalloc(&buf, total);
+  if (e != hipSuccess) return fail(REX_ENOMEM, "rex_render_set_visuals: hipMalloc: %s", hipGetErrorString(e));
+  char* b = static_cast<char*>(buf);
+  hipStream_t st = (hipStream_t)stream;
+  if (b_nodes) e = hipMemcpyAsync(b, nodes, b_nodes, hipMemcpyHostToDevice, st);
+  if (e == hipSuccess && b_tris) e = hipMemcpyAsync(b + o_tris, tris, b_tris, hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(b + o_root, inst_root, b_root, hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(b + o_box, inst_box, 24 * (size_t)num_inst, hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) e = hipStreamSynchronize(st);   // the host arrays are the caller's: done with them on return
+  if (e != hipSuccess) { (void)hipFree(buf); return fail(REX_EHIP, "rex_render_set_visuals: upload: %s", hipGetErrorString(e)); }
+  if (s->d_vis) (void)hipFree(s->d_vis);
+  s->d_vis = buf;
+  s->d_vis_nodes = reinterpret_cast<float*>(b);
+  s->d_vis_tris = reinterpret_cast<float*>(b + o_tris);
+  s->d_vis_root = reinterpret_cast<int32_t*>(b + o_root);
+  s->d_vis_box = reinterpret_cast<float*>(b + o_box);
+  return REX_OK;
+}
+
+int rex_render_visual(RexSim* s, const RexCamera* cam, const int32_t* d_env_ids, int n, int width, int height, uint8_t* d_rgb,
+                      float* d_depth, int16_t* d_seg, void* stream) {
+  rex::RenderCam rc;
+  const int rc_err = render_camera("rex_render_visual", s, cam, d_env_ids, n, width, height, d_rgb, rc);
+  if (rc_err != REX_OK) return rc_err;
+  if (!s->d_vis) return fail(REX_EINVAL, "rex_render_visual: no visual meshes set (rex_render_set_visuals)%s", "");
+  HIPCHK(hipSetDevice(s->device));
+  HIPCHK(rex_launch_render_mesh(s, rc, d_env_ids, n, width, height, d_rgb, d_depth, d_seg, (hipStream_t)stream));
   return REX_OK;
 }
 

@@ -406,10 +406,28 @@ class RexBatchEnv:
         _lib.check(self._L.rex_step(self._h, a.data_ptr(), out.p_obs, out.p_reward, out.p_done, self._p_cmd, self._stream_ptr()), "rex_step")
         return out.obs, out.reward, out.done_bool, self._info
 
-    def render(self, mode="rgb_array", env_ids=None, width=480, height=360, camera=None, depth=False, segmentation=False):
-        """Camera images of the batch (rex_render): the reference's RexGymEnv.render(mode="rgb_array") (rex_gym_env.py:416-439)
-        for many envs in one launch, on the env's stream, with no host sync.  The picture shows the collision geometry the
-        simulator uses (link boxes, full toe cylinders, the arm's collision cylinders), not the reference's meshes.
+    def load_visual_meshes(self, data_path=None):
+        """Read the URDF's visual meshes (rex_gym_amd/meshes.py; parsed and built once per process), build their BVHs and hand
+        them to the library (rex_render_set_visuals).  data_path = rex_gym.util.pybullet_data.getDataPath() (default: that
+        of an installed rex_gym).  Returns the loaded meshes; .missing lists the files not found, drawn as their links'
+        collision primitives.  After this, render() draws the meshes unless asked for geometry="collision"."""
+        from .. import meshes
+        vm = meshes.load(data_path, self.mark)
+        box = np.ascontiguousarray(np.concatenate([vm.lo, vm.hi], axis=1), dtype=np.float32)
+        with self._on_stream():
+            _lib.check(self._L.rex_render_set_visuals(self._h, vm.nodes.ctypes.data, len(vm.nodes), vm.tris.ctypes.data, len(vm.tris),
+                                                      vm.root.ctypes.data, box.ctypes.data, len(vm.root), self._stream_ptr()),
+                       "rex_render_set_visuals")
+        self._visuals = vm
+        return vm
+
+    def render(self, mode="rgb_array", env_ids=None, width=480, height=360, camera=None, depth=False, segmentation=False,
+               geometry=None):
+        """Camera images of the batch (rex_render / rex_render_visual): the reference's RexGymEnv.render(mode="rgb_array")
+        (rex_gym_env.py:416-439) for many envs in one launch, on the env's stream, with no host sync.  geometry "collision"
+        draws the collision geometry the simulator uses (link boxes, full toe cylinders, the arm's collision cylinders);
+        "visual" the URDF's visual meshes, as the reference draws them (loading them first with load_visual_meshes() from
+        the default location if this env has none); None = "visual" once meshes are loaded on this env, else "collision".
 
         env_ids: the envs to draw (default all), row k of the result is env env_ids[k].  camera: a dict (or _lib.RexCamera)
         with any of distance, yaw_deg, pitch_deg, fov_deg, near_plane, far_plane; the rest from the reference's camera
@@ -419,6 +437,10 @@ class RexBatchEnv:
         torch = self._torch
         if mode != "rgb_array":
             raise NotImplementedError(f"render mode {mode!r}: RexBatchEnv renders 'rgb_array' only (no GUI)")
+        if geometry is None:
+            geometry = "visual" if getattr(self, "_visuals", None) is not None else "collision"
+        if geometry not in ("collision", "visual"):
+            raise ValueError(f"render: geometry must be 'collision', 'visual' or None, got {geometry!r}")
         cam = self._camera(camera)
         width, height = int(width), int(height)
         if not (1 <= width <= 4096 and 1 <= height <= 4096):
@@ -438,12 +460,15 @@ class RexBatchEnv:
             k = int(ids.numel())
             if k * width * height * 3 >= 2 ** 31:
                 raise ValueError("render: k * width * height * 3 must stay below 2^31 bytes")
+            if geometry == "visual" and getattr(self, "_visuals", None) is None:
+                self.load_visual_meshes()
             rgb = torch.empty((k, height, width, 3), dtype=torch.uint8, device=self.device)
             dep = torch.empty((k, height, width), dtype=torch.float32, device=self.device) if depth else None
             seg = torch.empty((k, height, width), dtype=torch.int16, device=self.device) if segmentation else None
-            _lib.check(self._L.rex_render(self._h, ctypes.byref(cam), ids.data_ptr(), k, width, height, rgb.data_ptr(),
-                                          dep.data_ptr() if dep is not None else None, seg.data_ptr() if seg is not None else None,
-                                          self._stream_ptr()), "rex_render")
+            fn = "rex_render_visual" if geometry == "visual" else "rex_render"
+            _lib.check(getattr(self._L, fn)(self._h, ctypes.byref(cam), ids.data_ptr(), k, width, height, rgb.data_ptr(),
+                                            dep.data_ptr() if dep is not None else None, seg.data_ptr() if seg is not None else None,
+                                            self._stream_ptr()), fn)
         if depth or segmentation:
             return rgb, {"depth": dep, "segmentation": seg}
         return rgb

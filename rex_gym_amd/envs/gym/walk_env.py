@@ -47,10 +47,15 @@ class _SingleEnv:
         return (obs[0].cpu().numpy().astype(np.float64), float(rew[0].item()), bool(done[0].item()),
                 {"action": info["action"][0].cpu().numpy().astype(np.float64)})
 
+    def load_visual_meshes(self, data_path=None):
+        """Draw the URDF's visual meshes from now on (RexBatchEnv.load_visual_meshes): data_path =
+        rex_gym.util.pybullet_data.getDataPath(), default that of an installed rex_gym."""
+        return self._batch.load_visual_meshes(data_path)
+
     def render(self, mode="rgb_array", close=False):
         """mode 'rgb_array': a uint8 (360, 480, 3) frame of the follow camera (rex_gym_env.py:416-439), drawn by the HIP
-        renderer from the collision geometry; any other mode (the GUI's 'human') returns an empty array, as the reference
-        does outside rgb_array."""
+        renderer from the collision geometry, or from the URDF's visual meshes once load_visual_meshes() was called; any
+        other mode (the GUI's 'human') returns an empty array, as the reference does outside rgb_array."""
         if mode != "rgb_array":
             return np.array([])
         rgb = self._batch.render("rgb_array", width=480, height=360,

@@ -1,4 +1,4 @@
-"""Camera helpers of the renderer (rex_render, csrc/rex_render.hip) and a GIF writer.
+"""Camera helpers of the renderers (rex_render / rex_render_visual, csrc/rex_render.hip / rex_render_mesh.hip) and a GIF writer.
 
 The reference renders with PyBullet's getCameraImage (rex_gym/envs/rex_gym_env.py:416-439): a view matrix from
 computeViewMatrixFromYawPitchRoll, a projection from computeProjectionMatrixFOV, a 480 x 360 RGB frame.  The two matrix
@@ -6,7 +6,7 @@ functions below restate Bullet's conventions (b3ComputeViewMatrixFromYawPitchRol
 axis z) and return the same 16 floats, column-major, as PyBullet's functions of the same purpose do.  PyBullet is not
 available to this project, so these conventions are restated from Bullet's source and have NOT been checked against it;
 nor is the picture meant to agree pixel for pixel with PyBullet's renderer: the HIP renderer draws the collision geometry
-the simulator uses (link boxes, full toe cylinders), not the reference's visual meshes.
+the simulator uses (link boxes, full toe cylinders), or, once loaded, the URDF's visual meshes (flat-shaded, untextured).
 
 The view convention: start from eye = (0, -distance, 0) and up = (0, 0, 1), rotate both by Bullet's setEulerZYX(yaw, roll,
 pitch) -- Rz(yaw) Rx(pitch) when roll is 0 -- and add the target.  At yaw 0, pitch -30 the eye sits at

@@ -20,7 +20,8 @@ What it reproduces (marked UNVERIFIED against a live PyBull
     analytic cylinder segment about the toe-link y axis.
 
 With the reference's rex_arm.urdf present it also writes rex_arm_model_gen.h (the 6 arm bodies of mark 'arm') and
-rex_render_gen.h (the primitives the renderer draws: collision boxes and cylinders with the links' material colours).
+rex_render_gen.h (the primitives the renderer draws: collision boxes and cylinders with the links' material colours) and
+rex_visual_gen.h (the <visual> meshes of both URDFs: body, pose, file, scale, colour and a collision-primitive fallback).
 
 Usage: python tools/compile_model.py [--urdf PATH] [--out PATH]
 """
@@ -345,11 +346,8 @@ def frame_from_axis(a):
     return np.stack([x, np.cross(a, x), a], axis=1)
 
 
-def emit_render():
-    """rex_render_gen.h: the primitives the renderer draws (csrc/rex_render.hip) -- the collision geometry, not the visual meshes.
-    Mark 'base' = the REX_BOX_* boxes and the REX_TOE_* cylinders exactly as the physics uses them; mark 'arm' adds the
-    collision cylinders of the six arm links (drawn only: the physics does not collide them).  Colour = the link's visual
-    material; a merged fixed link keeps its own."""
+def render_prims():
+    """The primitives of rex_render_gen.h: [(kind, body, pos, R, ext, rgb, link)] and how many belong to mark 'base'."""
     bodies, links = load_bodies(DEFAULT_URDF, BASE_MOTOR_NAMES)
     colour = link_colours(DEFAULT_URDF)
     prims = []   # (kind, body, pos, R, ext, rgb, link)
@@ -386,6 +384,15 @@ def emit_render():
                               np.array([float(cyl.get("radius")), float(cyl.get("radius")), 0.5 * float(cyl.get("length"))]),
                               acolour[ln], ln))
     assert len(prims) == n_base + 6
+    return prims, n_base
+
+
+def emit_render():
+    """rex_render_gen.h: the primitives the renderer draws (csrc/rex_render.hip) -- the collision geometry, not the visual meshes.
+    Mark 'base' = the REX_BOX_* boxes and the REX_TOE_* cylinders exactly as the physics uses them; mark 'arm' adds the
+    collision cylinders of the six arm links (drawn only: the physics does not collide them).  Colour = the link's visual
+    material; a merged fixed link keeps its own."""
+    prims, n_base = render_prims()
     out = []
     w = out.append
     w("// GENERATED by tools/compile_model.py from the reference's rex.urdf / rex_arm.urdf -- do not edit.")
@@ -425,6 +432,102 @@ def emit_render():
     with open(DEFAULT_RENDER_OUT, "w") as f:
         f.write("\n".join(out) + "\n")
     print(f"wrote {DEFAULT_RENDER_OUT}: {n_base} + {len(prims) - n_base} primitives")
+
+
+DEFAULT_VISUAL_OUT = os.path.join(os.path.dirname(DEFAULT_OUT), "rex_visual_gen.h")
+
+
+def visual_entries(urdf, motor_names):
+    """One entry per <visual> of the URDF, in document order (commented-out blocks are not elements):
+    (link, body, pos, R, mesh path relative to assets/urdf/, scale, rgb).  The pose is the visual's frame in the frame of
+    the simulator body the link is merged into: the fixed-joint chain composed with the visual <origin>."""
+    bodies, _ = load_bodies(urdf, motor_names)
+    where = {ln: (bi, xyz, R) for bi, b in enumerate(bodies) for ln, xyz, R in b["members"]}
+    root = ET.parse(urdf).getroot()
+    named = {m.get("name"): [float(v) for v in m.find("color").get("rgba").split()][:3]
+             for m in root.findall("material") if m.find("color") is not None}
+    out = []
+    for l in root.findall("link"):
+        for v in l.findall("visual"):
+            mesh = v.find("geometry").find("mesh")
+            assert mesh is not None, l.get("name")
+            sc = [float(x) for x in (mesh.get("scale") or "1 1 1").split()]
+            assert sc[0] == sc[1] == sc[2], "non-uniform mesh scale"
+            m = v.find("material")
+            c = m.find("color")
+            rgb = [float(x) for x in c.get("rgba").split()][:3] if c is not None else named[m.get("name")]
+            vxyz, vrpy = parse_origin(v)
+            bi, xyz, R = where[l.get("name")]
+            out.append((l.get("name"), bi, xyz + R @ vxyz, R @ rpy_to_mat(vrpy), mesh.get("filename"), sc[0], rgb))
+    return out
+
+
+def emit_visual():
+    """rex_visual_gen.h: the visual meshes the mesh renderer draws (csrc/rex_render_mesh.hip, rex_gym_amd/meshes.py).  The
+    kernel reads body, pose and colour; Python parses the same header for the mesh files, scales and fallbacks."""
+    base = visual_entries(DEFAULT_URDF, BASE_MOTOR_NAMES)
+    arm = visual_entries(DEFAULT_ARM_URDF, BASE_MOTOR_NAMES + ARM_MOTOR_NAMES)
+    assert len(base) == 23 and len(arm) == 29
+    for a, b in zip(arm[:23], base):
+        assert a[0] == b[0] and a[1] == b[1] and a[4] == b[4] and np.allclose(a[2], b[2]) and np.allclose(a[3], b[3]), a[0]
+    ents = base + arm[23:]
+    prims, _ = render_prims()
+    fb = {}
+    for p in prims:   # a link's collision primitive (the toe: the full cylinder the physics uses) as drawn by rex_render
+        fb.setdefault(p[6], p)
+    out = []
+    w = out.append
+    w("// GENERATED by tools/compile_model.py from the reference's rex.urdf / rex_arm.urdf -- do not edit.")
+    w("// The visual meshes the mesh renderer draws (csrc/rex_render_mesh.hip): one entry per <visual> element.  Entries")
+    w("// 0..REX_VIS_N_BASE-1 are mark 'base' (rex.urdf); mark 'arm' draws all REX_VIS_N_ARM (rex_arm.urdf adds its six arm")
+    w("// links).  Each rides on body REX_VIS_BODY (numbered as in rex_model_gen.h, arm bodies 13..18): REX_VIS_POS / REX_VIS_ROT")
+    w("// place the mesh frame in that body's frame (fixed-joint chain composed with the visual <origin>; rotation row-major).")
+    w("// REX_VIS_MESH: the file relative to assets/urdf/, read at run time (rex_gym_amd/meshes.py) and scaled by REX_VIS_SCALE;")
+    w("// colour = the visual's <material>.  Fallback, drawn when the file is missing: the link's collision primitive as")
+    w("// rex_render_gen.h draws it (REX_RENDER_BOX / REX_RENDER_CYL; -1 = none), pose in the BODY frame.")
+    w("#ifndef REX_VISUAL_GEN_H")
+    w("#define REX_VISUAL_GEN_H")
+    w('#include "rex_render_gen.h"')
+    w("#define REX_VIS_N_BASE 23")
+    w(f"#define REX_VIS_N_ARM {len(ents)}")
+    w("REX_CONST int REX_VIS_BODY[REX_VIS_N_ARM] = {" + ", ".join(str(e[1]) for e in ents) + "};")
+    w("REX_CONST double REX_VIS_POS[REX_VIS_N_ARM][3] = {")
+    for e in ents:
+        w("  {" + ", ".join(fmt(v) for v in e[2]) + "},  /* " + e[0] + " */")
+    w("};")
+    w("REX_CONST double REX_VIS_ROT[REX_VIS_N_ARM][9] = {")
+    for e in ents:
+        w("  {" + ", ".join(fmt(v) for v in np.asarray(e[3]).ravel()) + "},")
+    w("};")
+    w("REX_CONST double REX_VIS_RGB[REX_VIS_N_ARM][3] = {")
+    for e in ents:
+        w("  {" + ", ".join(fmt(v) for v in e[6]) + "},")
+    w("};")
+    w("REX_CONST double REX_VIS_SCALE[REX_VIS_N_ARM] = {" + ", ".join(fmt(e[5]) for e in ents) + "};")
+    w("REX_CONST char REX_VIS_MESH[REX_VIS_N_ARM][32] = {")
+    for e in ents:
+        assert len(e[4]) < 32
+        w('  "' + e[4] + '",')
+    w("};")
+    w("REX_CONST int REX_VIS_FB_KIND[REX_VIS_N_ARM] = {" + ", ".join(str(fb[e[0]][0] if e[0] in fb else -1) for e in ents) + "};")
+    zero = (None, None, np.zeros(3), np.zeros((3, 3)), np.zeros(3))
+    w("REX_CONST double REX_VIS_FB_POS[REX_VIS_N_ARM][3] = {")
+    for e in ents:
+        assert e[0] not in fb or fb[e[0]][1] == e[1]
+        w("  {" + ", ".join(fmt(v) for v in fb.get(e[0], zero)[2]) + "},")
+    w("};")
+    w("REX_CONST double REX_VIS_FB_ROT[REX_VIS_N_ARM][9] = {")
+    for e in ents:
+        w("  {" + ", ".join(fmt(v) for v in np.asarray(fb.get(e[0], zero)[3]).ravel()) + "},")
+    w("};")
+    w("REX_CONST double REX_VIS_FB_EXT[REX_VIS_N_ARM][3] = {")
+    for e in ents:
+        w("  {" + ", ".join(fmt(v) for v in fb.get(e[0], zero)[4]) + "},")
+    w("};")
+    w("#endif /* REX_VISUAL_GEN_H */")
+    with open(DEFAULT_VISUAL_OUT, "w") as f:
+        f.write("\n".join(out) + "\n")
+    print(f"wrote {DEFAULT_VISUAL_OUT}: {len(base)} + {len(ents) - len(base)} visuals")
 
 
 def main():
@@ -640,3 +743,4 @@ if __name__ == "__main__":
     if os.path.exists(DEFAULT_ARM_URDF):
         emit_arm(load_bodies(DEFAULT_URDF, BASE_MOTOR_NAMES)[0])
         emit_render()
+        emit_visual()
