@@ -13,6 +13,11 @@
  *   envs/rex_gym_env.py:490-542    termination + reward, walk_env.py:356-362 observation
  * is done here for N environments at once by hand-written gfx950 kernels, one env per lane.
  *
+ * The agents' rollout loop -- a policy in the loop -- runs inside the launch as well: rex_set_policy (the
+ * feed-forward Gaussian MLP every shipped config uses) or rex_set_policy_recurrent (the GRU policy of
+ * agents/scripts/networks.py:113-159, on a caller-owned per-env state), then rex_step_policy /
+ * rex_step_segment_policy.
+ *
  * The reference has no FFI: its boundary is the Python Gym protocol.  The binding a maintainer
  * adds is a ctypes stub; `rex_gym_amd/envs` is that stub plus the Gym surface.
  *
@@ -344,6 +349,35 @@ REX_API int rex_step_policy(RexSim* sim, const float* d_obs_in, float* d_action,
  * A caller that keeps one block obs[T + 1, N, obs_dim] passes d_obs_in = obs[0], d_obs = obs[1]: prevob of step t is obs[t]. */
 REX_API int rex_step_segment_policy(RexSim* sim, int num_steps, const float* d_obs_in, float* d_action, float* d_mean, float* d_obs,
              float* d_reward, uint8_t* d_done, float* d_motor_cmd, void* stream);
+
+/* ---- the RECURRENT actor inside the launch (no ABI bump: a new entry point and struct, nothing existing changes) ----
+ * The other network of the reference's agents (agents/scripts/networks.py:113-159 RecurrentGaussianPolicy): the last policy layer is
+ * tf.contrib.rnn.GRUBlockCell(state_size) on a per-env state h that starts from zero with every episode:
+ *   x = relu(W1 filt(obs) + b1);  r, u = sigmoid(Wg [x, h] + bg);  c = tanh(Wc [x, r.h] + bc);  h' = u.h + (1 - u).c;  mean = tanh(W3 h' + b3)
+ * (the reset gate acts BEFORE the candidate's product: TensorFlow's cell, not torch.nn.GRU).  rex_step_policy / rex_step_segment_policy
+ * run the policy installed LAST by rex_set_policy or rex_set_policy_recurrent; NULL to either removes it.  The weights are snapshotted
+ * as rex_set_policy's are.  d_state is NOT: it is the live state [state_size][N] (word-major like the state block), read in front of
+ * every perform() and written back behind it, so it must stay valid while the policy is installed.  An env whose episode starts --
+ * behind rex_reset (which also zeroes its state rows while a recurrent policy is installed) or behind an in-launch auto-reset -- acts
+ * on h = 0; the row of an env whose episode has just ended inside a launch keeps its last h until that next perform().
+ * Same restrictions as rex_set_policy.  obs_dim + 12 + hidden1 + 2 state_size floats (each term rounded up to a multiple of 4) per env
+ * must fit the kernel's contact-row region of LDS: 200 + 100 does on every variant. */
+typedef struct RexRecurrentPolicy {
+  int32_t obs_dim, action_dim;            /* must equal rex_obs_dim / rex_action_dim of the sim's config */
+  int32_t hidden1, state_size;            /* the ReLU layer in front of the cell; the cell's width, 1..128 (the reference: 100) */
+  const float* d_w1; const float* d_b1;   /* [obs_dim][hidden1], [hidden1] */
+  const float* d_wg; const float* d_bg;   /* [hidden1 + state_size][2 state_size], [2 state_size]: inputs x then h; units r then u */
+  const float* d_wc; const float* d_bc;   /* [hidden1 + state_size][state_size], [state_size]: inputs x then r.h */
+  const float* d_w3; const float* d_b3;   /* [state_size][action_dim], [action_dim]: the mean layer on h', tanh on top */
+  const float* d_logstd;                  /* [action_dim] */
+  const float* d_obs_mean;                /* as RexPolicy */
+  const float* d_obs_scale;
+  float   obs_clip;
+  int32_t sample;
+  uint64_t seed;
+  float*  d_state;                        /* [state_size][N], caller-owned, live */
+} RexRecurrentPolicy;
+REX_API int rex_set_policy_recurrent(RexSim* sim, const RexRecurrentPolicy* policy, void* stream);
 
 /* HIP event timing of rex_step launches on their own stream (ms).  rex_set_timing(1): one event pair, read with
  * rex_last_step_ms (synchronises on the launch).  rex_set_timing(2): a ring of event pairs around the last 256 launches,

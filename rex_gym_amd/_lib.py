@@ -47,6 +47,18 @@ class RexPolicy(ctypes.Structure):
     ]
 
 
+class RexRecurrentPolicy(ctypes.Structure):
+    """Mirror of `struct RexRecurrentPolicy` (include/rexsim.h): the recurrent actor (a GRU cell on a live per-env state)."""
+    _fields_ = [
+        ("obs_dim", ctypes.c_int32), ("action_dim", ctypes.c_int32), ("hidden1", ctypes.c_int32), ("state_size", ctypes.c_int32),
+        ("d_w1", ctypes.c_void_p), ("d_b1", ctypes.c_void_p), ("d_wg", ctypes.c_void_p), ("d_bg", ctypes.c_void_p),
+        ("d_wc", ctypes.c_void_p), ("d_bc", ctypes.c_void_p), ("d_w3", ctypes.c_void_p), ("d_b3", ctypes.c_void_p), ("d_logstd", ctypes.c_void_p),
+        ("d_obs_mean", ctypes.c_void_p), ("d_obs_scale", ctypes.c_void_p),
+        ("obs_clip", ctypes.c_float), ("sample", ctypes.c_int32), ("seed", ctypes.c_uint64),
+        ("d_state", ctypes.c_void_p),
+    ]
+
+
 class RexCamera(ctypes.Structure):
     """Mirror of `struct RexCamera` (include/rexsim.h): the follow camera of rex_render (angles in degrees)."""
     _fields_ = [("distance", ctypes.c_float), ("yaw_deg", ctypes.c_float), ("pitch_deg", ctypes.c_float),
@@ -79,6 +91,7 @@ _SIGS = {
     "rex_step_segment": ([ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                           ctypes.c_void_p, ctypes.c_void_p], ctypes.c_int),
     "rex_set_policy": ([ctypes.c_void_p, ctypes.POINTER(RexPolicy), ctypes.c_void_p], ctypes.c_int),
+    "rex_set_policy_recurrent": ([ctypes.c_void_p, ctypes.POINTER(RexRecurrentPolicy), ctypes.c_void_p], ctypes.c_int),
     "rex_step_policy": ([ctypes.c_void_p] + [ctypes.c_void_p] * 8, ctypes.c_int),
     "rex_step_segment_policy": ([ctypes.c_void_p, ctypes.c_int] + [ctypes.c_void_p] * 8, ctypes.c_int),
     "rex_set_timing": ([ctypes.c_void_p, ctypes.c_int], ctypes.c_int),

@@ -505,14 +505,14 @@ def train_segments(env, agent, steps, segment=25, training=True, actor=None, see
     out with the policy and the filter as they stood at its start (the reference's perform() sees the filter of the step before).
 
     steps: control steps of every env (rounded up to whole segments).  Returns the mean score and length of the episodes that ended.
-    `actor`: a FusedActor to reuse between calls (else one is made and left installed in the env)."""
+    `actor`: a FusedActor to reuse between calls (else one is made and left installed in the env).
+    PPOConfig(network="recurrent"): the GRU state is the actor's (`actor.state`), reset by the kernel at episode boundaries; when the
+    call returns agent.state holds it, so a caller may go on with train()."""
     from .fused_actor import FusedActor
     dev, cfg, n = agent.device, agent.cfg, agent.n
     T = int(segment)
     if not env.config.auto_reset or not env.config.range_normalize or env.config.max_episode_steps != cfg.max_length:
         raise ValueError("train_segments: create the env with auto_reset=True, range_normalize=True, max_episode_steps=agent.cfg.max_length")
-    if agent.state is not None:
-        raise NotImplementedError("the recurrent policy runs through train(): its GRU state is not carried by the fused actor")
     if actor is None:
         actor = FusedActor(env, agent.net, agent.observ_filter, sample=training, seed=seed)
     O, A, Tmax = env.obs_dim, env.action_dim, cfg.max_length
@@ -568,6 +568,11 @@ def train_segments(env, agent, steps, segment=25, training=True, actor=None, see
         agent.episode_length.copy_(torch.where(total == 0, len0 + T, T - 1 - last_done[-1]))
         score0 = torch.where(total == 0, score0 + csum[-1], csum[-1] - csum.gather(0, last_done[-1:].clamp(min=0))[0])
         obs[0].copy_(obs[T])
+    if agent.state is not None:
+        # the recurrent policy: its GRU state lives in the actor's device buffer (the kernel starts every episode from zero); hand it
+        # to the agent, with the rows of the envs whose episode ended at the very last step zeroed as begin_episode would
+        agent.state = actor.state.clone()
+        agent.state[done[-1].bool()] = 0.0
     if not scores:
         return float("nan"), float("nan")
     return float(torch.cat(scores).mean()), float(torch.cat(lengths).float().mean())
@@ -586,6 +591,8 @@ if __name__ == "__main__":   # python -m rex_gym_amd.agents.ppo --task walk --en
                     help="segments: the actor inside the launch, one launch per --segment steps (train_segments); steps: perform() in PyTorch, "
                          "one launch and three host synchronisations per step (train, the reference's loop shape)")
     ap.add_argument("--segment", type=int, default=25)
+    ap.add_argument("--network", default="forward", choices=["forward", "recurrent"],
+                    help="forward: ForwardGaussianPolicy (every shipped config); recurrent: RecurrentGaussianPolicy, a GRU cell as the last policy layer")
     ap.add_argument("--toe-friction", type=float, default=None, help="pin the toe friction (RexBatchEnv(friction_range=(f, f))); the standup task matches its "
                                                                      "PyBullet record at 0.25 (DESIGN.md section 2)")
     ap.add_argument("--logdir", default=None, help="write the trained policy there as a TensorFlow-1 checkpoint the reference's policy player "
@@ -596,7 +603,7 @@ if __name__ == "__main__":   # python -m rex_gym_amd.agents.ppo --task walk --en
     env = RexBatchEnv(a.envs, task=a.task, signal_type=a.signal, seed=a.seed, max_episode_steps=a.max_length, range_normalize=True,
                       gait_clock_scale=a.gait_clock_scale, auto_reset=a.loop == "segments", check_actions=False,
                       **({"friction_range": (a.toe_friction, a.toe_friction)} if a.toe_friction is not None else {}))
-    agent = PPOAgent(a.envs, env.obs_dim, env.action_dim, PPOConfig(update_every=a.envs, max_length=a.max_length), seed=a.seed)
+    agent = PPOAgent(a.envs, env.obs_dim, env.action_dim, PPOConfig(update_every=a.envs, max_length=a.max_length, network=a.network), seed=a.seed)
     actor = None
     if a.loop == "segments":
         from .fused_actor import FusedActor

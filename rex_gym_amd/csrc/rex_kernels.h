@@ -864,17 +864,21 @@ __device__ __forceinline__ void gather_legs(const SM& sm, int leg0, EnvState& e,
 // and one-wave workgroups keep a multi-round launch (> 16 384 envs) from waiting for the slowest of four waves before a CU takes new work
 // (65 536 walk-IK envs, fused actor per step: 68.9 M env-steps/s with four-wave workgroups)
 #define REX_POLICY_WAVES(EPW) ((EPW) <= 8 ? 4 : 1)
-template <int EPW, bool ARM, bool MIXED, bool BODY, bool TRACE = false, bool SEG = false, bool POLICY = false>
-__global__ __launch_bounds__(POLICY ? REX_WAVE * REX_POLICY_WAVES(EPW) : REX_WAVE) REX_STEP_KERNEL_ATTR void rex_step_kernel(DevCfg c, float* __restrict__ state, const float* __restrict__ snap,
+template <int EPW, bool ARM, bool MIXED, bool BODY, bool TRACE = false, bool SEG = false, bool POLICY = false, bool RNN = false>
+__global__ __launch_bounds__(POLICY && !RNN ? REX_WAVE * REX_POLICY_WAVES(EPW) : REX_WAVE) REX_STEP_KERNEL_ATTR void rex_step_kernel(DevCfg c, float* __restrict__ state, const float* __restrict__ snap,
                                                             const float* __restrict__ action0, float* __restrict__ obs_out0,
                                                             float* __restrict__ reward_out0, uint8_t* __restrict__ done_out0,
-                                                            float* __restrict__ cmd_out0, typename PolArg<POLICY>::type pol) {
+                                                            float* __restrict__ cmd_out0, typename PolArg<POLICY, RNN>::type pol) {
   // POLICY (the instantiations behind rex_step_policy / rex_step_segment_policy; the base and arm step units are compiled once more with
   // -DREX_TU_POL=1): a SEG kernel whose actions are not read from action0 but computed, step by step, by the reference's Gaussian MLP
   // actor on the observation the env returned last (rex_policy.h) -- a closed-loop rollout segment in one launch.  Their workgroup is
   // FOUR waves (one per SIMD of a CU, each with its own envs and its own LDS rows exactly as a one-wave workgroup has them) that share
   // one copy of the actor's weights in dynamic LDS, loaded once per launch, where it fits next to the rows (pol.in_lds; else the weights
   // are streamed from L2 every step).
+  // RNN (POLICY kernels compiled a fifth time, -DREX_TU_RNN=1, behind rex_set_policy_recurrent): the actor's last hidden layer is the
+  // reference's GRU cell on a per-env state in the caller's buffer pol.state.  Its weights (364 KB for 4-200-(100)-2) do not fit in LDS
+  // and are streamed at every envs-per-wave, so the workgroup is ONE wave, placed like the plain segment kernels'.
+  static_assert(!RNN || POLICY, "the recurrent actor is a fused actor");
   static_assert(!POLICY || (SEG && !MIXED && !BODY && !TRACE && EPW <= 16), "the fused actor: segment kernels of the single-task lane-group variants");
   // SEG (the instantiations behind rex_step_segment; every step translation unit is compiled once more with -DREX_TU_SEG=1): one launch =
   // c.nsteps consecutive env.step() calls of the shard, a rollout segment whose actions the caller already holds -- action0 /
@@ -896,7 +900,7 @@ __global__ __launch_bounds__(POLICY ? REX_WAVE * REX_POLICY_WAVES(EPW) : REX_WAV
   constexpr int kRowsF4 = ARM ? REX_LDS_F4_PER_ENV_ARM_OF(EPW) : REX_ROWS_F4_OF(kLegF4);
   static_assert(!BODY || EPW <= 16, "link-box contact rows: lane-group kernels only");
   constexpr int kWaveF4 = (kRowsF4 + (EPW <= 16 ? REX_PARK_F4_OF(EPW, ARM) : 0) + (BODY ? REX_BODY_F4 : 0)) * EPW;
-  constexpr int kWaves = POLICY ? REX_POLICY_WAVES(EPW) : 1;     // waves of this workgroup (each works as a one-wave workgroup does)
+  constexpr int kWaves = POLICY && !RNN ? REX_POLICY_WAVES(EPW) : 1;     // waves of this workgroup (each works as a one-wave workgroup does)
   __shared__ float4 lds_wg[kWaveF4 * kWaves];
   float4* const lds = lds_wg + (kWaves > 1 ? (int)(threadIdx.x >> 6) * kWaveF4 : 0);     // this wave's rows
   REX_STAMP(t_kernel);
@@ -907,7 +911,7 @@ __global__ __launch_bounds__(POLICY ? REX_WAVE * REX_POLICY_WAVES(EPW) : REX_WAV
   const int wg_block = kWaves > 1 ? (int)blockIdx.x * kWaves + (int)(threadIdx.x >> 6) : (int)blockIdx.x;   // the one-wave block this wave stands for
   if (c.clock && lane == 0) atomicMin(&c.clock[2 * (wg_block & (REX_CLOCK_WAYS - 1))], (unsigned long long)wall_clock64());
   const float* pol_wl = nullptr;          // POLICY: the actor's weights in LDS (null: streamed)
-  if constexpr (POLICY) {
+  if constexpr (POLICY && !RNN) {
     extern __shared__ float4 rex_dyn_lds[];
     if (pol.in_lds) {
       policy_weights_to_lds(pol, policy_offsets(c.obs_dim, c.action_dim, pol.h1, pol.h2).total, reinterpret_cast<float*>(rex_dyn_lds), (int)threadIdx.x,
@@ -940,7 +944,7 @@ __global__ __launch_bounds__(POLICY ? REX_WAVE * REX_POLICY_WAVES(EPW) : REX_WAV
     mixed_config_of_task(c, c.block_task[blk], cmix);        // wave-uniform: the task's constants stay in SGPRs
     cmix.max_repeat = cmix.action_repeat; cmix.max_iterations = cmix.iterations;
   } else {
-    if constexpr (EPW < 16 && !POLICY) {   // (a four-wave workgroup covers whole sectors by itself)
+    if constexpr (EPW < 16 && (!POLICY || RNN)) {   // (a four-wave workgroup covers whole sectors by itself)
       constexpr int G = 16 / EPW;
       const int full = ((int)gridDim.x / (8 * G)) * (8 * G);
       if (blk < full) { const int xcd = blk & 7, q = blk >> 3; blk = ((q / G) * 8 + xcd) * G + (q % G); }
@@ -982,7 +986,9 @@ __global__ __launch_bounds__(POLICY ? REX_WAVE * REX_POLICY_WAVES(EPW) : REX_WAV
     // algo.perform(prevob) (agents/ppo/algorithm.py:105-134): the observation of the previous step -- slice seg_step - 1 of the
     // segment's observation block, stored by this wave in front of the fence that ended that step; the caller's obs_in for the first
     const float* obs_prev = seg_step == 0 ? pol.obs_in : obs_out0 + (unsigned)((seg_step - 1) * c.n * c.obs_dim);
-    if (pol_wl) policy_act<EPW, LPE, ARM, true>(c, pol, pol_wl, reinterpret_cast<float*>(lds), lane, slot, pl, leg0, i, ingrid, e.episode, e.steps, obs_prev,
+    if constexpr (RNN) policy_act<EPW, LPE, ARM, false, true>(c, pol, nullptr, reinterpret_cast<float*>(lds), lane, slot, pl, leg0, i, ingrid, e.episode, e.steps, obs_prev,
+                                                        (unsigned)(seg_step * c.n * c.action_dim), act, pol.state);
+    else if (pol_wl) policy_act<EPW, LPE, ARM, true>(c, pol, pol_wl, reinterpret_cast<float*>(lds), lane, slot, pl, leg0, i, ingrid, e.episode, e.steps, obs_prev,
                                                 (unsigned)(seg_step * c.n * c.action_dim), act);
     else policy_act<EPW, LPE, ARM, false>(c, pol, nullptr, reinterpret_cast<float*>(lds), lane, slot, pl, leg0, i, ingrid, e.episode, e.steps, obs_prev,
                                           (unsigned)(seg_step * c.n * c.action_dim), act);
@@ -1315,7 +1321,9 @@ struct RexSim {
   rex::PolDev pol;       // rex_set_policy: the actor of rex_step_policy / rex_step_segment_policy
   float* d_polbuf;       // the packed actor (library-owned; rex_policy.h policy_offsets) and its capacity in floats
   int polbuf_floats;
-  int have_policy;
+  int have_policy;        // 0: none, 1: the forward actor (rex_set_policy), 2: the recurrent one (rex_set_policy_recurrent) -- the one installed last
+  float* d_rnn_state;     // the recurrent actor's GRU state [state_size][n]: caller-owned, live
+  int rnn_state_size;
   bool use_policy;        // this launch runs the fused-actor kernels (set by step_launch)
   int pol_attr_bytes;     // the dynamic-LDS limit this sim has already set on its fused-actor kernel (hipFuncSetAttribute)
   int pol_lds_bytes;      // dynamic LDS of the fused-actor kernels: the weights' copy (0: they do not fit next to four waves' rows and are streamed)
@@ -1346,6 +1354,8 @@ void rex_launch_step_mixed_arm_seg(RexSim* s, int blocks, hipStream_t st, const 
 void rex_launch_step_body_seg(RexSim* s, int blocks, hipStream_t st, const float* a, float* o, float* r, uint8_t* d, float* m);
 void rex_launch_step_base_pol(RexSim* s, int blocks, hipStream_t st, const float* a, float* o, float* r, uint8_t* d, float* m);
 void rex_launch_step_arm_pol(RexSim* s, int blocks, hipStream_t st, const float* a, float* o, float* r, uint8_t* d, float* m);
+void rex_launch_step_base_rnn(RexSim* s, int blocks, hipStream_t st, const float* a, float* o, float* r, uint8_t* d, float* m);
+void rex_launch_step_arm_rnn(RexSim* s, int blocks, hipStream_t st, const float* a, float* o, float* r, uint8_t* d, float* m);
 void rex_launch_settle_base(RexSim* s, int nrec, hipStream_t st, float* snap);   // <false, *>
 void rex_launch_settle_arm(RexSim* s, int nrec, hipStream_t st, float* snap);    // <true, *>
 
@@ -1360,12 +1370,17 @@ void rex_launch_settle_arm(RexSim* s, int nrec, hipStream_t st, float* snap);   
 #ifndef REX_TU_POL
 #define REX_TU_POL 0      /* -DREX_TU_POL=1: the fused-actor instantiations (rex_step_policy / rex_step_segment_policy; launcher names end in _pol) */
 #endif
+#ifndef REX_TU_RNN
+#define REX_TU_RNN 0      /* -DREX_TU_RNN=1: the recurrent fused-actor instantiations (rex_set_policy_recurrent; launcher names end in _rnn) */
+#endif
 #if REX_TU_TRACE
 #define REX_STEP_LAUNCHER(group) rex_launch_step_##group##_trace
 #elif REX_TU_SEG
 #define REX_STEP_LAUNCHER(group) rex_launch_step_##group##_seg
 #elif REX_TU_POL
 #define REX_STEP_LAUNCHER(group) rex_launch_step_##group##_pol
+#elif REX_TU_RNN
+#define REX_STEP_LAUNCHER(group) rex_launch_step_##group##_rnn
 #else
 #define REX_STEP_LAUNCHER(group) rex_launch_step_##group
 #endif
@@ -1381,8 +1396,19 @@ static void rex_launch_policy_kernel(RexSim* s, int blocks, hipStream_t st, cons
   hipLaunchKernelGGL(kern, dim3((blocks + W - 1) / W), dim3(REX_WAVE * W), (size_t)s->pol_lds_bytes, st,
                      s->dev, s->d_state, s->d_snap, a, o, r, d, m, s->pol);
 }
+// the recurrent fused-actor kernels: one-wave workgroups, no dynamic LDS (the weights are streamed)
+template <int EPW, bool ARM>
+static void rex_launch_rnn_kernel(RexSim* s, int blocks, hipStream_t st, const float* a, float* o, float* r, uint8_t* d, float* m) {
+  rex::RnnDev pol;
+  static_cast<rex::PolDev&>(pol) = s->pol;
+  pol.state = s->d_rnn_state;
+  hipLaunchKernelGGL((rex::rex_step_kernel<EPW, ARM, false, false, false, true, true, true>), dim3(blocks), dim3(REX_WAVE), 0, st,
+                     s->dev, s->d_state, s->d_snap, a, o, r, d, m, pol);
+}
 #if REX_TU_POL
 #define REX_LAUNCH_STEP(EPW, ARM, MIXED, BODY) rex_launch_policy_kernel<EPW, ARM>(s, blocks, st, a, o, r, d, m)
+#elif REX_TU_RNN
+#define REX_LAUNCH_STEP(EPW, ARM, MIXED, BODY) rex_launch_rnn_kernel<EPW, ARM>(s, blocks, st, a, o, r, d, m)
 #else
 #define REX_LAUNCH_STEP(EPW, ARM, MIXED, BODY)                                                                                  \
   hipLaunchKernelGGL((rex::rex_step_kernel<EPW, ARM, MIXED, BODY, REX_TU_TRACE != 0, REX_TU_SEG != 0, false>), dim3(blocks), dim3(REX_WAVE), 0, st, s->dev, s->d_state, s->d_snap, \

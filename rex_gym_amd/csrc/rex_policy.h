@@ -22,6 +22,12 @@
 // else they are streamed from L2 every step, two chunks in flight.  The hidden activations use the contact-row region of LDS,
 // idle between two env steps.
 // What a perform() costs a wave (tools/microbench/policy_mb.hip, profiles/r06_mb_policy.txt): DESIGN.md section 5.
+//
+// The RECURRENT actor (rex_set_policy_recurrent; networks.py:113-159 RecurrentGaussianPolicy; template flag RNN): the second ReLU layer
+// is tf.contrib.rnn.GRUBlockCell(S) on a per-env state h kept in the caller's buffer [S][n] --
+//   r = sigmoid(Wr [x, h] + br), u = sigmoid(Wu [x, h] + bu), c = tanh(Wc [x, r.h] + bc), h' = u.h + (1 - u).c, mean = tanh(W3 h' + b3)
+// -- three 128-unit MFMA passes (dense_gate_mfma) that overwrite dead values in LDS (t = r.h, then c over t, then h' over h), so the
+// default 200 + 100 shape fits the contact-row region of every variant; its weights (364 KB) are streamed from L2.
 #pragma once
 #include <type_traits>
 
@@ -60,11 +66,43 @@ struct PolDev {
   int32_t in_lds;                        // the launch carries dynamic LDS for the packed actor: one copy per workgroup
 };
 struct NoPol {};
-template <bool POLICY> struct PolArg { using type = NoPol; };
-template <> struct PolArg<true> { using type = PolDev; };
+// the RECURRENT actor (rex_set_policy_recurrent; networks.py:113-159 RecurrentGaussianPolicy): PolDev with h2 = the cell's width S, plus
+// the caller's live GRU state [S][n] (word-major like the state block), read in front of every perform() and written back behind it
+struct RnnDev : PolDev { float* state; };
+template <bool POLICY, bool RNN = false> struct PolArg { using type = NoPol; };
+template <> struct PolArg<true, false> { using type = PolDev; };
+template <> struct PolArg<true, true> { using type = RnnDev; };
+
+// the packed recurrent actor: one ReLU layer of H1 units, then TensorFlow's GRUBlockCell of S units as THREE matrices of S units each
+// (reset gate, update gate, candidate), every one over the inputs [x (H1, padded to whole quads), h or r.h (S, padded)]: a 128-unit MFMA
+// pass each (S <= 128).  Same conventions as policy_offsets: [k / 4][unit][4], blocks on 16-byte boundaries, REX_POLICY_SLACK zeros.
+struct RnnOff { int w1, b1, wr, br, wu, bu, wc, bc, w3, b3, logstd, mean, scale, total; };
+__host__ __device__ __forceinline__ RnnOff rnn_offsets(int O, int A, int H1, int S) {
+  RnnOff o;
+  auto up4 = [](int n) { return (n + 3) & ~3; };
+  const int gate = (pol_q4(H1) + pol_q4(S)) * S * 4;   // [ceil(H1 / 4) + ceil(S / 4)][S][4], zero rows beyond H1 and beyond S
+  o.w1 = 0;
+  o.b1 = o.w1 + pol_q4(O) * H1 * 4;
+  o.wr = o.b1 + up4(H1);
+  o.br = o.wr + gate;
+  o.wu = o.br + up4(S);
+  o.bu = o.wu + gate;
+  o.wc = o.bu + up4(S);
+  o.bc = o.wc + gate;
+  o.w3 = o.bc + up4(S);                    // [S][A]
+  o.b3 = o.w3 + up4(S * A);
+  o.logstd = o.b3 + up4(A);
+  o.mean = o.logstd + up4(A);
+  o.scale = o.mean + up4(O);
+  o.total = o.scale + up4(O) + REX_POLICY_SLACK;
+  return o;
+}
+#define REX_RNN_MAX_STATE 128   /* one MFMA pass per gate */
 
 // floats of LDS scratch per env of the wave: x [4 ceil(O / 4)], meta [4], action [8], h1 [4 ceil(H1 / 4)], h2 [4 ceil(H2 / 4)]
 __host__ __device__ __forceinline__ int policy_scratch_floats(int obs_dim, int h1, int h2) { return 4 * pol_q4(obs_dim) + 12 + 4 * pol_q4(h1) + 4 * pol_q4(h2); }
+// the recurrent actor: x [4 ceil(O / 4)], meta [4], action [8], relu layer [4 ceil(H1 / 4)], h [4 ceil(S / 4)], t [4 ceil(S / 4)] (r.h, then c)
+__host__ __device__ __forceinline__ int rnn_scratch_floats(int obs_dim, int h1, int s) { return 4 * pol_q4(obs_dim) + 12 + 4 * pol_q4(h1) + 8 * pol_q4(s); }
 #define REX_POLICY_NOISE_BLOCK 64   /* Philox block numbers (gauss4) of the action sample: behind the sensor-noise call sites */
 #ifdef REX_POL_PROF      /* tools/microbench/policy_mb.hip: cycle counters of the sections of a perform() */
 __device__ long long g_pol_prof[8];
@@ -151,6 +189,71 @@ __device__ __forceinline__ void dense_relu_mfma(const float* Wp, const float* Bv
   }
 }
 
+// One gate of the GRU cell on the matrix cores: v[j][e] = B[j] + sum_k W[k][j] [inA, inB][k][e] for N <= 128 units (ONE pass), handed quad
+// by quad to epi(float4 index into an [N / 4][E][4] activation array, the four units' sums) instead of being stored.  The inputs are
+// two LDS arrays read one behind the other (KqA quads of inA, then Kq - KqA of inB): [x, h] and [x, r.h] without a copy.  Chunks, the two
+// accumulators per (unit half, env group) and the order of the fmaf chains are dense_relu_mfma's.  A wave's LDS accesses execute in
+// program order and epi runs behind the pass's last read, so epi may overwrite the pass's own inputs.
+template <int E, class Epi>
+__device__ __forceinline__ void dense_gate_mfma(const float* Wp, const float* Bv, int KqA, int Kq, int N, const float* inA, const float* inB, int lane, Epi epi) {
+  constexpr int G = E / 4;
+  constexpr int KC = G == 1 ? 4 : 2;
+  const int blk = lane >> 2, jj = lane & 3;
+  const float4* a4 = reinterpret_cast<const float4*>(inA) + jj;
+  const float4* b4 = reinterpret_cast<const float4*>(inB) + jj - KqA * E;
+  const float4* w4 = reinterpret_cast<const float4*>(Wp) + lane;
+  const float4 bl = *reinterpret_cast<const float4*>(Bv + 4 * blk), bh = *reinterpret_cast<const float4*>(Bv + REX_WAVE + 4 * blk);
+  pol_f4 d0[G][2], d1[G][2];
+#pragma unroll
+  for (int g = 0; g < G; ++g) {
+    d0[g][0] = pol_f4{bl.x, bl.y, bl.z, bl.w}; d1[g][0] = pol_f4{bh.x, bh.y, bh.z, bh.w};
+    d0[g][1] = pol_f4{0.0f, 0.0f, 0.0f, 0.0f}; d1[g][1] = pol_f4{0.0f, 0.0f, 0.0f, 0.0f};
+  }
+  struct Chunk { float4 w0[KC], w1[KC], x[KC][G]; };
+  auto fetch = [&](int q0, Chunk& c) {
+#pragma unroll
+    for (int k = 0; k < KC; ++k) {
+      const int q = min(q0 + k, Kq - 1);
+      c.w0[k] = w4[q * N]; c.w1[k] = w4[q * N + REX_WAVE];
+      const float4* in4 = (q < KqA ? a4 : b4) + q * E;             // (wave-uniform)
+#pragma unroll
+      for (int g = 0; g < G; ++g) c.x[k][g] = in4[4 * g];
+    }
+  };
+  auto consume = [&](int q0, const Chunk& c) {
+#pragma unroll
+    for (int k = 0; k < KC; ++k) {
+      if (q0 + k < Kq) {
+#pragma unroll
+        for (int g = 0; g < G; ++g) {
+          d0[g][0] = __builtin_amdgcn_mfma_f32_4x4x1f32(c.w0[k].x, c.x[k][g].x, d0[g][0], 0, 0, 0); d1[g][0] = __builtin_amdgcn_mfma_f32_4x4x1f32(c.w1[k].x, c.x[k][g].x, d1[g][0], 0, 0, 0);
+          d0[g][1] = __builtin_amdgcn_mfma_f32_4x4x1f32(c.w0[k].y, c.x[k][g].y, d0[g][1], 0, 0, 0); d1[g][1] = __builtin_amdgcn_mfma_f32_4x4x1f32(c.w1[k].y, c.x[k][g].y, d1[g][1], 0, 0, 0);
+        }
+#pragma unroll
+        for (int g = 0; g < G; ++g) {
+          d0[g][0] = __builtin_amdgcn_mfma_f32_4x4x1f32(c.w0[k].z, c.x[k][g].z, d0[g][0], 0, 0, 0); d1[g][0] = __builtin_amdgcn_mfma_f32_4x4x1f32(c.w1[k].z, c.x[k][g].z, d1[g][0], 0, 0, 0);
+          d0[g][1] = __builtin_amdgcn_mfma_f32_4x4x1f32(c.w0[k].w, c.x[k][g].w, d0[g][1], 0, 0, 0); d1[g][1] = __builtin_amdgcn_mfma_f32_4x4x1f32(c.w1[k].w, c.x[k][g].w, d1[g][1], 0, 0, 0);
+        }
+      }
+    }
+  };
+  Chunk ca, cb;
+  fetch(0, ca);
+  for (int q0 = 0; q0 < Kq; q0 += 2 * KC) {
+    fetch(q0 + KC, cb);
+    consume(q0, ca);
+    fetch(q0 + 2 * KC, ca);
+    consume(q0 + KC, cb);
+  }
+  const int q_lo = blk, q_hi = blk + REX_WAVE / 4;
+#pragma unroll
+  for (int g = 0; g < G; ++g) {
+    if (4 * q_lo < N) epi(q_lo * E + 4 * g + jj, d0[g][0] + d0[g][1]);
+    if (4 * q_hi < N) epi(q_hi * E + 4 * g + jj, d1[g][0] + d1[g][1]);
+  }
+}
+__device__ __forceinline__ float pol_sigmoid(float v) { return 1.0f / (1.0f + expf(-v)); }
+
 template <int LP>
 __device__ __forceinline__ float lanes_sum(float v) {     // over LP adjacent lanes (1, 2, 4, 8), every lane of the run gets the total
   if (LP >= 2) v += dpp_f<kDppXor1>(v);
@@ -164,13 +267,21 @@ __device__ __forceinline__ float lanes_sum(float v) {     // over LP adjacent la
 // (reset, or the previous step of this segment: written by this very wave, in front of the workgroup fence that ends a step).
 // sc: this wave's LDS scratch, 16-byte aligned, policy_scratch_floats() * EPW floats.  wl: the packed actor in LDS
 // (policy_weights_to_lds, shared by the workgroup's waves), or null: streamed from p.pk.
-template <int EPW, int LPE, bool ARM, bool INLDS>
+// RNN: the recurrent actor (rnn_offsets; p.h2 = S): the second ReLU layer is the GRU cell on the env's state hstate[k * c.n + env], which
+// starts from zero with every episode (steps == 0: behind rex_reset or an in-launch auto-reset) and is stored back behind the cell.
+template <int EPW, int LPE, bool ARM, bool INLDS, bool RNN = false>
 __device__ __forceinline__ void policy_act(const DevCfg& c, const PolDev& p, const float* wl, float* sc, int lane, int slot, int pl, int leg0, int i, bool valid,
-                                           int episode, int steps, const float* obs_prev, unsigned out_off, float* act) {
+                                           int episode, int steps, const float* obs_prev, unsigned out_off, float* act, float* hstate = nullptr) {
   constexpr int E = EPW;
   static_assert(EPW % 4 == 0 && EPW <= 16, "lane-group kernels only");
+  static_assert(!(RNN && INLDS), "the recurrent actor's weights are streamed");
   const int O = c.obs_dim, A = c.action_dim, H1 = p.h1, H2 = p.h2;
-  const PolOff o = policy_offsets(O, A, H1, H2);
+  PolOff o;
+  RnnOff ro;
+  if constexpr (RNN) {
+    ro = rnn_offsets(O, A, H1, H2);
+    o.w1 = ro.w1; o.b1 = ro.b1; o.w3 = ro.w3; o.b3 = ro.b3; o.logstd = ro.logstd; o.mean = ro.mean; o.scale = ro.scale;
+  } else o = policy_offsets(O, A, H1, H2);
   const float* pw = INLDS ? wl : p.pk;                             // (an LDS pointer or a global one: the two instantiations keep them apart)
   float* xs = sc;
   int* meta = reinterpret_cast<int*>(sc + 4 * pol_q4(O) * E);
@@ -209,8 +320,42 @@ __device__ __forceinline__ void policy_act(const DevCfg& c, const PolDev& p, con
   dense_relu_mfma<E>(pw + o.w1, pw + o.b1, pol_q4(O), H1, xs, h1s, lane);
   mirror_sync();
   REX_POL_STAMP(1);
+  if constexpr (RNN) {
+    // ---- the GRU cell (TensorFlow's GRUBlockCell: the reset gate acts BEFORE the candidate's product) on h2s = h, ts = scratch ----
+    const int S = H2, Sq = pol_q4(S), Kq = pol_q4(H1) + Sq;
+    float* ts = h2s + 4 * Sq * E;
+    for (int idx = lane; idx < 4 * Sq * E; idx += REX_WAVE) {      // h of the wave's envs (zero at the start of an episode, zero padding)
+      const int e = idx & (E - 1), k = idx / E;
+      h2s[((k >> 2) * E + e) * 4 + (k & 3)] = (k < S && meta[2 * E + e] != 0) ? hstate[(size_t)k * c.n + meta[e]] : 0.0f;
+    }
+    mirror_sync();
+    float4* h4 = reinterpret_cast<float4*>(h2s);
+    float4* t4 = reinterpret_cast<float4*>(ts);
+    // three passes of one code: r = sigmoid(Wr [x, h] + br), t = r . h;  c = tanh(Wc [x, t] + bc) over t in place;
+    // u = sigmoid(Wu [x, h] + bu), h' = u . h + (1 - u) . c over h in place
+#pragma clang loop unroll(disable)
+    for (int pass = 0; pass < 3; ++pass) {
+      const int wo = pass == 0 ? ro.wr : (pass == 1 ? ro.wc : ro.wu), bo = pass == 0 ? ro.br : (pass == 1 ? ro.bc : ro.bu);
+      dense_gate_mfma<E>(pw + wo, pw + bo, pol_q4(H1), Kq, S, h1s, pass == 1 ? ts : h2s, lane, [&](int at, pol_f4 v) {
+        if (pass == 1) { t4[at] = make_float4(tanhf(v[0]), tanhf(v[1]), tanhf(v[2]), tanhf(v[3])); return; }
+        const float4 h = h4[at];
+        const float g0 = pol_sigmoid(v[0]), g1 = pol_sigmoid(v[1]), g2 = pol_sigmoid(v[2]), g3 = pol_sigmoid(v[3]);
+        if (pass == 0) t4[at] = make_float4(g0 * h.x, g1 * h.y, g2 * h.z, g3 * h.w);
+        else {
+          const float4 cc = t4[at];
+          h4[at] = make_float4(fmaf(g0, h.x, (1.0f - g0) * cc.x), fmaf(g1, h.y, (1.0f - g1) * cc.y), fmaf(g2, h.z, (1.0f - g2) * cc.z), fmaf(g3, h.w, (1.0f - g3) * cc.w));
+        }
+      });
+      mirror_sync();
+    }
+    for (int idx = lane; idx < S * E; idx += REX_WAVE) {           // the new state, back to the caller's buffer (one slot per real env)
+      const int e = idx & (E - 1), k = idx / E;
+      if (meta[3 * E + e]) hstate[(size_t)k * c.n + meta[e]] = h2s[((k >> 2) * E + e) * 4 + (k & 3)];
+    }
+  } else {
   dense_relu_mfma<E>(pw + o.w2, pw + o.b2, pol_q4(H1), H2, h1s, h2s, lane);     // the bulk: h1 x h2 x EPW fmas
   mirror_sync();
+  }
   REX_POL_STAMP(2);
   // ---- the mean layer and the sample: LP adjacent lanes per (action word, env), each a slice of the inputs, one DPP sum ----
   auto head = [&](auto lp_tag) {

@@ -32,6 +32,45 @@ __global__ void rex_pack_policy_kernel(PolSrc s, int O, int A, int H1, int H2, f
   }
 }
 
+// rex_set_policy_recurrent: the same for the recurrent actor (rnn_offsets).  A gate matrix [ceil(H1 / 4) + ceil(S / 4)][S][4] takes
+// its rows from the caller's [H1 + S][ld] matrix: the x rows, zero rows up to a whole quad, the h rows, zero rows; columns col0 + j.
+struct RnnSrc { const float *w1, *b1, *wg, *bg, *wc, *bc, *w3, *b3, *logstd, *mean, *scale; };
+__device__ __forceinline__ float rnn_gate_weight(int u, int H1, int S, const float* src, int ld, int col0) {
+  const int r = u & 3, j = (u >> 2) % S, q = (u >> 2) / S;
+  int row;
+  if (q < pol_q4(H1)) { row = 4 * q + r; if (row >= H1) return 0.0f; }
+  else { row = 4 * (q - pol_q4(H1)) + r; if (row >= S) return 0.0f; row += H1; }
+  return src[row * ld + col0 + j];
+}
+__global__ void rex_pack_rnn_kernel(RnnSrc s, int O, int A, int H1, int S, float* __restrict__ dst) {
+  const RnnOff o = rnn_offsets(O, A, H1, S);
+  for (int t = blockIdx.x * blockDim.x + threadIdx.x; t < o.total; t += gridDim.x * blockDim.x) {
+    float v = 0.0f;
+    if (t < o.b1) { const int r = t & 3, j = (t >> 2) % H1, k = 4 * ((t >> 2) / H1) + r; if (k < O) v = s.w1[k * H1 + j]; }
+    else if (t < o.wr) { if (t - o.b1 < H1) v = s.b1[t - o.b1]; }
+    else if (t < o.br) v = rnn_gate_weight(t - o.wr, H1, S, s.wg, 2 * S, 0);
+    else if (t < o.wu) { if (t - o.br < S) v = s.bg[t - o.br]; }
+    else if (t < o.bu) v = rnn_gate_weight(t - o.wu, H1, S, s.wg, 2 * S, S);
+    else if (t < o.wc) { if (t - o.bu < S) v = s.bg[S + t - o.bu]; }
+    else if (t < o.bc) v = rnn_gate_weight(t - o.wc, H1, S, s.wc, S, 0);
+    else if (t < o.w3) { if (t - o.bc < S) v = s.bc[t - o.bc]; }
+    else if (t < o.b3) { if (t - o.w3 < S * A) v = s.w3[t - o.w3]; }
+    else if (t < o.logstd) { if (t - o.b3 < A) v = s.b3[t - o.b3]; }
+    else if (t < o.mean) { if (t - o.logstd < A) v = s.logstd[t - o.logstd]; }
+    else if (t < o.scale) { if (t - o.mean < O && s.mean) v = s.mean[t - o.mean]; }
+    else if (t < o.scale + O) { v = s.scale ? s.scale[t - o.scale] : 1.0f; }
+    dst[t] = v;
+  }
+}
+// rex_reset while a recurrent policy is installed: the GRU state rows [S][n] of the reset envs start from zero
+__global__ void rex_zero_rnn_state_kernel(float* __restrict__ state, int n, int S, const int32_t* __restrict__ indices, int count) {
+  const int r = blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= count) return;
+  const int i = indices ? indices[r] : r;
+  if (i < 0 || i >= n) return;
+  for (int k = 0; k < S; ++k) state[(size_t)k * n + i] = 0.0f;
+}
+
 
 // Regrouping of a large batch (one workgroup): counting sort of the env indices by the solver sweeps of the last step,
 // most sweeps first (the long waves start first), 64 bins.  perm[k] = env of wave slot k.  The order inside a bin does
@@ -429,7 +468,7 @@ int rex_create(const RexConfig* cfg, int device, float* d_state, void* stream, R
   s->d_state = d_state;
   s->timing = 0;
   s->have_timing = 0;
-  s->have_policy = 0; s->use_policy = false;
+  s->have_policy = 0; s->use_policy = false; s->d_rnn_state = nullptr; s->rnn_state_size = 0;
   rex::DevCfg& d = s->dev;
   d.n = cfg->num_envs; d.env_index_base = cfg->env_index_base; d.task = cfg->task; d.signal = cfg->signal;
   d.nsteps = 1;
@@ -667,6 +706,11 @@ int rex_reset(RexSim* s, const int32_t* d_indices, int n, float* d_obs, void* st
     hipLaunchKernelGGL(rex::rex_reset_kernel<12>, dim3((count + block - 1) / block), dim3(block), 0, (hipStream_t)stream, s->dev,
                        s->d_state, s->d_snap, d_indices, count, d_obs);
   HIPCHK(hipGetLastError());
+  if (s->have_policy == 2) {   // the recurrent actor: an episode starts from a zero GRU state
+    hipLaunchKernelGGL(rex::rex_zero_rnn_state_kernel, dim3((count + block - 1) / block), dim3(block), 0, (hipStream_t)stream, s->d_rnn_state,
+                       s->cfg.num_envs, s->rnn_state_size, d_indices, count);
+    HIPCHK(hipGetLastError());
+  }
   return REX_OK;
 }
 
@@ -739,10 +783,51 @@ int rex_set_policy(RexSim* s, const RexPolicy* p, void* stream) {
   return REX_OK;
 }
 
+int rex_set_policy_recurrent(RexSim* s, const RexRecurrentPolicy* p, void* stream) {
+  if (!s) return fail(REX_EINVAL, "rex_set_policy_recurrent: null sim%s", "");
+  if (!p) { s->have_policy = 0; return REX_OK; }
+  if (s->cfg.task == REX_TASK_MIXED || s->cfg.body_contacts || s->epw > 16)
+    return fail(REX_EINVAL, "rex_set_policy_recurrent: the fused actor runs in the single-task lane-group kernels (not REX_TASK_MIXED, body_contacts = 0, REX_ENVS_PER_WAVE <= 16)%s", "");
+  if (!s->cfg.range_normalize)
+    return fail(REX_EINVAL, "rex_set_policy_recurrent: the sim must fold the reference's wrapper stack (RexConfig.range_normalize = 1): the agents act through "
+                            "RangeNormalize + ClipAction (playground/trainer.py:48-52)%s", "");
+  if (p->obs_dim != rex_obs_dim(&s->cfg) || p->action_dim != rex_action_dim(&s->cfg))
+    return failf(REX_EINVAL, "rex_set_policy_recurrent: obs_dim / action_dim %d / %d do not match the sim's %d / %d", p->obs_dim, p->action_dim, rex_obs_dim(&s->cfg), rex_action_dim(&s->cfg));
+  if (p->state_size < 1 || p->state_size > REX_RNN_MAX_STATE)
+    return failf(REX_EINVAL, "rex_set_policy_recurrent: state_size %d: the cell is one matrix-core pass per gate, 1..%d units", p->state_size, REX_RNN_MAX_STATE);
+  if (p->hidden1 < 1 || p->hidden1 > 4096 || rex::rnn_scratch_floats(p->obs_dim, p->hidden1, p->state_size) > rows_floats_per_env(s))
+    return failf(REX_EINVAL, "rex_set_policy_recurrent: a layer of %d units and a cell of %d need %d floats of LDS per env, this kernel variant has %d", p->hidden1, p->state_size,
+                 rex::rnn_scratch_floats(p->obs_dim, p->hidden1 > 0 ? p->hidden1 : 0, p->state_size), rows_floats_per_env(s));
+  if (!p->d_w1 || !p->d_b1 || !p->d_wg || !p->d_bg || !p->d_wc || !p->d_bc || !p->d_w3 || !p->d_b3 || !p->d_logstd || (!p->d_obs_mean) != (!p->d_obs_scale))
+    return fail(REX_EINVAL, "rex_set_policy_recurrent: null weight pointer (d_obs_mean and d_obs_scale go together)%s", "");
+  if (!p->d_state) return fail(REX_EINVAL, "rex_set_policy_recurrent: null d_state (the GRU state [state_size][num_envs] is caller-owned)%s", "");
+  if (!(p->obs_clip > 0.0f) && p->d_obs_mean) return fail(REX_EINVAL, "rex_set_policy_recurrent: obs_clip must be positive%s", "");
+  HIPCHK(hipSetDevice(s->device));
+  const rex::RnnOff off = rex::rnn_offsets(p->obs_dim, p->action_dim, p->hidden1, p->state_size);
+  if (off.total > s->polbuf_floats) {            // (the buffer is shared with rex_set_policy: one policy is installed at a time)
+    if (s->d_polbuf) { HIPCHK(hipDeviceSynchronize()); (void)hipFree(s->d_polbuf); s->d_polbuf = nullptr; s->polbuf_floats = 0; }
+    if (hipMalloc(&s->d_polbuf, sizeof(float) * (size_t)off.total) != hipSuccess) return fail(REX_ENOMEM, "rex_set_policy_recurrent: hipMalloc%s", "");
+    s->polbuf_floats = off.total;
+  }
+  rex::RnnSrc src{p->d_w1, p->d_b1, p->d_wg, p->d_bg, p->d_wc, p->d_bc, p->d_w3, p->d_b3, p->d_logstd, p->d_obs_mean, p->d_obs_scale};
+  hipLaunchKernelGGL(rex::rex_pack_rnn_kernel, dim3((off.total + 255) / 256), dim3(256), 0, (hipStream_t)stream, src, p->obs_dim, p->action_dim, p->hidden1,
+                     p->state_size, s->d_polbuf);
+  HIPCHK(hipGetLastError());
+  rex::PolDev& d = s->pol;
+  d.pk = s->d_polbuf; d.obs_in = nullptr; d.action_out = nullptr; d.mean_out = nullptr;
+  d.h1 = p->hidden1; d.h2 = p->state_size; d.obs_clip = p->d_obs_mean ? p->obs_clip : 0.0f; d.sample = p->sample ? 1 : 0;
+  d.seed_lo = (uint32_t)p->seed; d.seed_hi = (uint32_t)(p->seed >> 32);
+  d.in_lds = 0;                                  // 364 KB for 4-200-(100)-2: streamed from L2 at every envs-per-wave
+  s->pol_lds_bytes = 0;
+  s->d_rnn_state = p->d_state; s->rnn_state_size = p->state_size;
+  s->have_policy = 2;
+  return REX_OK;
+}
+
 static int policy_launch(RexSim* s, const char* who, int num_steps, const float* d_obs_in, float* d_action, float* d_mean, float* d_obs, float* d_reward,
                          uint8_t* d_done, float* d_motor_cmd, void* stream) {
   if (!s || !d_obs_in || !d_action || !d_obs || !d_reward || !d_done) return fail(REX_EINVAL, "%s: null pointer", who);
-  if (!s->have_policy) return fail(REX_EINVAL, "%s: no policy set (rex_set_policy)", who);
+  if (!s->have_policy) return fail(REX_EINVAL, "%s: no policy set (rex_set_policy / rex_set_policy_recurrent)", who);
   if (s->dev.trace) return fail(REX_EINVAL, "%s: not available while an event trace is set (rex_set_event_trace)", who);
   if (num_steps < 1) return fail(REX_EINVAL, "%s: num_steps must be at least 1", who);
   if (d_obs_in == d_obs) return fail(REX_EINVAL, "%s: d_obs must not alias d_obs_in", who);
@@ -1068,7 +1153,8 @@ static void launch_step(RexSim* s, int blocks, hipStream_t st, const float* a, f
     return;
   }
   if (s->use_policy) {       // rex_step_policy / rex_step_segment_policy: the segment kernels with the actor in front of every step
-    if (arm) rex_launch_step_arm_pol(s, blocks, st, a, o, r, d, m); else rex_launch_step_base_pol(s, blocks, st, a, o, r, d, m);
+    if (s->have_policy == 2) { if (arm) rex_launch_step_arm_rnn(s, blocks, st, a, o, r, d, m); else rex_launch_step_base_rnn(s, blocks, st, a, o, r, d, m); }
+    else if (arm) rex_launch_step_arm_pol(s, blocks, st, a, o, r, d, m); else rex_launch_step_base_pol(s, blocks, st, a, o, r, d, m);
     return;
   }
   if (s->dev.nsteps > 1) {   // rex_step_segment: the instantiations with the loop over the segment's steps

@@ -577,6 +577,43 @@ class RexBatchEnv:
         _lib.check(self._L.rex_set_policy(self._h, ctypes.byref(pol), self._stream_ptr()), "rex_set_policy")
         self._policy = True
 
+    def set_policy_recurrent(self, w1=None, b1=None, wg=None, bg=None, wc=None, bc=None, w3=None, b3=None, logstd=None, state=None,
+                             obs_mean=None, obs_scale=None, obs_clip=5.0, sample=True, seed=0):
+        """Install the RECURRENT actor (include/rexsim.h `RexRecurrentPolicy`): the reference's RecurrentGaussianPolicy
+        (agents/scripts/networks.py:113-159) -- one ReLU layer, then TensorFlow's GRU cell of S units, then the tanh mean layer.  As
+        set_policy: contiguous float32 device tensors, INPUT-major weights: w1 [obs_dim, h1], wg [h1 + S, 2 S] (inputs x then h, units r
+        then u), wc [h1 + S, S], w3 [S, action_dim].  The weights are snapshotted; `state` [S, num_envs] is not: the launches read and
+        write it at every step, reset() zeroes the rows (columns of this tensor) of the envs it resets, and it must stay alive while
+        the policy is installed (the env keeps a reference).  set_policy_recurrent(None) removes the policy."""
+        torch = self._torch
+        if w1 is None:
+            _lib.check(self._L.rex_set_policy_recurrent(self._h, None, None), "rex_set_policy_recurrent")
+            self._policy = None
+            self._policy_state = None
+            return
+        ts = dict(w1=w1, b1=b1, wg=wg, bg=bg, wc=wc, bc=bc, w3=w3, b3=b3, logstd=logstd, state=state)
+        if (obs_mean is None) != (obs_scale is None):
+            raise ValueError("obs_mean and obs_scale go together")
+        if obs_mean is not None:
+            ts.update(obs_mean=obs_mean, obs_scale=obs_scale)
+        for name, t in ts.items():
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.device != self.device or not t.is_contiguous():
+                raise ValueError(f"set_policy_recurrent: {name} must be a contiguous float32 tensor on {self.device}")
+        h1, S = int(w1.shape[1]) if w1.dim() == 2 else -1, int(wc.shape[1]) if wc.dim() == 2 else -1
+        want = dict(w1=(self.obs_dim, h1), b1=(h1,), wg=(h1 + S, 2 * S), bg=(2 * S,), wc=(h1 + S, S), bc=(S,), w3=(S, self.action_dim),
+                    b3=(self.action_dim,), logstd=(self.action_dim,), state=(S, self.num_envs), obs_mean=(self.obs_dim,), obs_scale=(self.obs_dim,))
+        for name, t in ts.items():
+            if tuple(t.shape) != want[name]:
+                raise ValueError(f"set_policy_recurrent: {name} has shape {tuple(t.shape)}, expected {want[name]}")
+        pol = _lib.RexRecurrentPolicy()
+        pol.obs_dim, pol.action_dim, pol.hidden1, pol.state_size = self.obs_dim, self.action_dim, h1, S
+        for name in ("w1", "b1", "wg", "bg", "wc", "bc", "w3", "b3", "logstd", "obs_mean", "obs_scale", "state"):
+            setattr(pol, "d_" + name, ts[name].data_ptr() if name in ts else None)
+        pol.obs_clip, pol.sample, pol.seed = float(obs_clip), int(bool(sample)), int(seed) & (2 ** 64 - 1)
+        _lib.check(self._L.rex_set_policy_recurrent(self._h, ctypes.byref(pol), self._stream_ptr()), "rex_set_policy_recurrent")
+        self._policy = True
+        self._policy_state = state
+
     def _policy_blocks(self, T, obs_in, out, action, mean, motor_cmd):
         torch = self._torch
         if self._needs_reset:
