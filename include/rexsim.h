@@ -246,6 +246,31 @@ REX_API int rex_set_heightfield(RexSim* sim, const float* d_heights, const float
  * the ones computed at load.  NULL restores (1, 1, 0.5). */
 REX_API int rex_set_body_params(RexSim* sim, const float* d_params);
 
+/* The actuator half of the randomisation hooks: the knobs of the reference's MotorModel (model/motor.py:40-74: set_voltage,
+ * set_viscous_damping, set_strength_ratios, set_motor_gains) per env.
+ * Per-env actuator parameters, read by every step: caller-owned device array [4 + num_motors][num_envs], word-major like d_state:
+ * row 0 battery voltage [V] (motor.py MOTOR_VOLTAGE), 1 viscous damping, 2 kp, 3 kd, 4 + m strength ratio of motor m (order of
+ * mark_constants).  NULL restores the nominal motor (32 V, 0, RexConfig.motor_kp / motor_kd, 1).  The reset motion is the
+ * nominal robot's, as with rex_set_body_params.  In the order of motor.py:116-143: observed = clip(KT pwm V / R), net voltage
+ * = clip(pwm V - (KT + damping) qd_true, +-50), the current table, actual torque *= strength -- the overheat protection
+ * (rex.py:603) sees the torque after the strength ratio.  Not offered together with the debug event trace (rex_set_event_trace):
+ * whichever of the two is set second returns REX_EINVAL. */
+REX_API int rex_set_motor_params(RexSim* sim, const float* d_params);
+
+/* Per-reset draws inside the launch (what an env_randomizer would do after Rex.Reset): on every episode start env g draws
+ * each quantity ~ U(lo, hi) from its Philox stream; lo == hi == 0: that quantity is not drawn (it keeps its nominal value, or its
+ * rex_set_motor_params entry).  strength_per_motor: 1 = one draw per motor, 0 = one per env for all its motors.
+ * NULL: off.  REX_EINVAL for lo > hi, negative bounds, a zero upper voltage bound with a non-zero lower one, NaN.
+ * The draws are a pure function of (seed, GLOBAL env index, episode ordinal) -- they do not depend on sharding, on the envs
+ * per wave or on the segment length, nothing is stored, and they work with auto_reset and inside segment launches -- and use
+ * Philox counter words of their own: a rollout with mass / friction ranges is the same with and without them. */
+typedef struct RexMotorRandom { float strength_lo, strength_hi, voltage_lo, voltage_hi, damping_lo, damping_hi,
+                                      kp_lo, kp_hi, kd_lo, kd_hi; int32_t strength_per_motor; } RexMotorRandom;
+REX_API int rex_set_motor_randomization(RexSim* sim, const RexMotorRandom* r);
+
+/* The parameters in effect for every env's CURRENT episode, same layout, to a caller-owned device buffer (one small launch). */
+REX_API int rex_get_motor_params(RexSim* sim, float* d_out, void* stream);
+
 /* Debug: trace the discrete events of the restated stepSimulation.  d_trace: caller-owned device buffer uint32 [3][num_envs]
  * (NULL switches the trace off, the default; the caller zeroes it).  While set, every substep folds into word [0][i] of env i
  * which toe points are within the contact breaking distance, the heightfield facet under each of them (under the toe end's
@@ -405,6 +430,9 @@ REX_API int rex_ik_solve(int n, const float* d_orn, const float* d_pos, const fl
 REX_API int rex_motor_torque(int n, const float* d_cmd, const float* d_q, const float* d_qd,
                      const float* d_qd_true, float kp, float kd,
                      float* d_actual, float* d_observed, void* stream);
+/* Controller-only twin of rex_motor_torque with per-problem parameters: d_par [n][5] = kp, kd, voltage, damping, strength. */
+REX_API int rex_motor_torque_params(int n, const float* d_cmd, const float* d_q, const float* d_qd, const float* d_qd_true,
+                                    const float* d_par, float* d_actual, float* d_observed, void* stream);
 /* model/gait_planner.py:96-134 with the phase clock on explicit time `now`.
  * mode: 0 walk, 1 gallop.  d_planner [n,3] = (phi, last_time, alpha) in/out; params[n,6] =
  * (v, angle_deg, w_rot, period, direction, now) -- both float64: the clock values and the phase decide branches and must

@@ -59,6 +59,13 @@ class RexRecurrentPolicy(ctypes.Structure):
     ]
 
 
+class RexMotorRandom(ctypes.Structure):
+    """Mirror of `struct RexMotorRandom` (include/rexsim.h): per-reset uniform ranges of the actuator's knobs (lo == hi == 0: not drawn)."""
+    _fields_ = [("strength_lo", ctypes.c_float), ("strength_hi", ctypes.c_float), ("voltage_lo", ctypes.c_float), ("voltage_hi", ctypes.c_float),
+                ("damping_lo", ctypes.c_float), ("damping_hi", ctypes.c_float), ("kp_lo", ctypes.c_float), ("kp_hi", ctypes.c_float),
+                ("kd_lo", ctypes.c_float), ("kd_hi", ctypes.c_float), ("strength_per_motor", ctypes.c_int32)]
+
+
 class RexCamera(ctypes.Structure):
     """Mirror of `struct RexCamera` (include/rexsim.h): the follow camera of rex_render (angles in degrees)."""
     _fields_ = [("distance", ctypes.c_float), ("yaw_deg", ctypes.c_float), ("pitch_deg", ctypes.c_float),
@@ -81,6 +88,9 @@ _SIGS = {
                     ctypes.POINTER(ctypes.c_void_p)], ctypes.c_int),
     "rex_destroy": ([ctypes.c_void_p], ctypes.c_int),
     "rex_set_body_params": ([ctypes.c_void_p, ctypes.c_void_p], ctypes.c_int),
+    "rex_set_motor_params": ([ctypes.c_void_p, ctypes.c_void_p], ctypes.c_int),
+    "rex_set_motor_randomization": ([ctypes.c_void_p, ctypes.POINTER(RexMotorRandom)], ctypes.c_int),
+    "rex_get_motor_params": ([ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p], ctypes.c_int),
     "rex_set_history": ([ctypes.c_void_p, ctypes.c_void_p], ctypes.c_int),
     "rex_set_terrain": ([ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p], ctypes.c_int),
     "rex_set_heightfield": ([ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
@@ -101,6 +111,7 @@ _SIGS = {
     "rex_motor_torque": ([ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                           ctypes.c_float, ctypes.c_float, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p],
                          ctypes.c_int),
+    "rex_motor_torque_params": ([ctypes.c_int] + [ctypes.c_void_p] * 8, ctypes.c_int),
     "rex_gait_loop": ([ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                        ctypes.c_void_p], ctypes.c_int),
     "rex_set_event_trace": ([ctypes.c_void_p, ctypes.c_void_p], ctypes.c_int),

@@ -2,7 +2,7 @@
 
 The library is compiled variant group by variant group -- one translation unit per group of rex_step_kernel /
 rex_settle_kernel instantiations (csrc/rex_step_*.hip, rex_settle_*.hip) next to the C ABI (csrc/rexsim.hip) -- in
-parallel, then linked (27 jobs: the step units are compiled three times, base and arm twice more, see TRACE_SOURCES ... RNN_SOURCES) where the single translation
+parallel, then linked (36 jobs: the step units are compiled four times, base and arm four times more, see TRACE_SOURCES ... MOT_SOURCES) where the single translation
 unit took over 2 minutes.
 
 Developer knobs (never needed for the product build):
@@ -37,6 +37,12 @@ POL_SOURCES = ["rex_step_arm.hip", "rex_step_base.hip"]
 # ... and a fifth time with -DREX_TU_RNN=1: the same with the reference's RECURRENT actor (a GRU cell on a per-env state,
 # rex_set_policy_recurrent), kept apart so that the forward actor's kernels stay exactly what they were
 RNN_SOURCES = POL_SOURCES
+# ... and the segment, fused-actor and recurrent units once more with -DREX_TU_MOT=1: the same kernels reading the per-env actuator
+# parameters (rex_set_motor_params / rex_set_motor_randomization; rex_step runs them as a segment of one step), kept apart because the
+# parameter loads and draws cost registers: every other kernel stays exactly what it was
+MOT_SOURCES = [(s, "_mseg") for s in SEG_SOURCES] + [(s, "_mpol") for s in POL_SOURCES] + [(s, "_mrnn") for s in RNN_SOURCES]
+TAG_DEFINES = {"_trace": ["-DREX_TU_TRACE=1"], "_seg": ["-DREX_TU_SEG=1"], "_pol": ["-DREX_TU_POL=1"], "_rnn": ["-DREX_TU_RNN=1"],
+               "_mseg": ["-DREX_TU_SEG=1", "-DREX_TU_MOT=1"], "_mpol": ["-DREX_TU_POL=1", "-DREX_TU_MOT=1"], "_mrnn": ["-DREX_TU_RNN=1", "-DREX_TU_MOT=1"]}
 HEADERS = sorted(f for f in os.listdir(CSRC) if f.endswith(".h"))   # every header the sources can include
 # -ffp-contract=on: a * b + c inside one expression is one fma and nothing else is fused -- the arithmetic of a kernel is fixed by its
 # source and does not depend on what else is compiled into it (hipcc's default lets the backend fuse across statements by heuristics:
@@ -56,7 +62,7 @@ def _hipcc():
 def _flags_stamp():
     # the compile flags fix the kernels' arithmetic (-ffp-contract=on): a flags-only edit of this file must rebuild too
     import hashlib
-    return hashlib.sha256(" ".join(HIPCC_FLAGS + POL_SOURCES + ["rnn"] + RNN_SOURCES).encode()).hexdigest()[:16]
+    return hashlib.sha256(" ".join(HIPCC_FLAGS + POL_SOURCES + ["rnn"] + RNN_SOURCES + ["mot"] + [s + t for s, t in MOT_SOURCES]).encode()).hexdigest()[:16]
 
 
 def needs_build(lib_path=None):
@@ -129,6 +135,19 @@ def build(force=False, verbose=False, lib_path=None, defines=(), unity=False, on
                         "#define REX_STEP_LAUNCHER(group) rex_launch_step_##group##_rnn\n"
                         "#define REX_LAUNCH_STEP(EPW, ARM, MIXED, BODY) rex_launch_rnn_kernel<EPW, ARM>(s, blocks, st, a, o, r, d, m)\n")
                 f.write("".join('#include "%s"\n' % os.path.join(CSRC, s) for s in RNN_SOURCES))
+                f.write("#undef REX_STEP_LAUNCHER\n#undef REX_LAUNCH_STEP\n#undef REX_TU_RNN\n#define REX_TU_RNN 0\n#undef REX_TU_MOT\n#define REX_TU_MOT 1\n"
+                        "#define REX_STEP_LAUNCHER(group) rex_launch_step_##group##_mseg\n"
+                        "#define REX_LAUNCH_STEP(EPW, ARM, MIXED, BODY) hipLaunchKernelGGL((rex::rex_step_kernel<EPW, ARM, MIXED, BODY, false, true, false, false, true>), "
+                        "dim3(blocks), dim3(REX_WAVE), 0, st, s->dev, s->d_state, s->d_snap, a, o, r, d, m, rex_step_arg<true>(s, rex::NoPol{}))\n")
+                f.write("".join('#include "%s"\n' % os.path.join(CSRC, s) for s in SEG_SOURCES))
+                f.write("#undef REX_STEP_LAUNCHER\n#undef REX_LAUNCH_STEP\n#undef REX_TU_POL\n#define REX_TU_POL 1\n"
+                        "#define REX_STEP_LAUNCHER(group) rex_launch_step_##group##_mpol\n"
+                        "#define REX_LAUNCH_STEP(EPW, ARM, MIXED, BODY) rex_launch_policy_kernel<EPW, ARM, true>(s, blocks, st, a, o, r, d, m)\n")
+                f.write("".join('#include "%s"\n' % os.path.join(CSRC, s) for s in POL_SOURCES))
+                f.write("#undef REX_STEP_LAUNCHER\n#undef REX_LAUNCH_STEP\n#undef REX_TU_POL\n#define REX_TU_POL 0\n#undef REX_TU_RNN\n#define REX_TU_RNN 1\n"
+                        "#define REX_STEP_LAUNCHER(group) rex_launch_step_##group##_mrnn\n"
+                        "#define REX_LAUNCH_STEP(EPW, ARM, MIXED, BODY) rex_launch_rnn_kernel<EPW, ARM, true>(s, blocks, st, a, o, r, d, m)\n")
+                f.write("".join('#include "%s"\n' % os.path.join(CSRC, s) for s in RNN_SOURCES))
             cmd = [hipcc] + flags + ["-shared", uni, "-o", lib_path]
             if verbose:
                 print(" ".join(cmd))
@@ -136,7 +155,7 @@ def build(force=False, verbose=False, lib_path=None, defines=(), unity=False, on
             _stamp(lib_path, defines, only)
             return lib_path
         jobs_list = []
-        for s, trace in [(s, "") for s in SOURCES] + [(s, "_trace") for s in TRACE_SOURCES] + [(s, "_seg") for s in SEG_SOURCES] + [(s, "_pol") for s in POL_SOURCES] + [(s, "_rnn") for s in RNN_SOURCES]:
+        for s, trace in [(s, "") for s in SOURCES] + [(s, "_trace") for s in TRACE_SOURCES] + [(s, "_seg") for s in SEG_SOURCES] + [(s, "_pol") for s in POL_SOURCES] + [(s, "_rnn") for s in RNN_SOURCES] + MOT_SOURCES:
             src = os.path.join(CSRC, s)
             tag = trace
             if keep is not None and s in GROUPS and GROUPS[s] not in keep:
@@ -144,7 +163,7 @@ def build(force=False, verbose=False, lib_path=None, defines=(), unity=False, on
                 with open(src, "w") as f:
                     f.write(_stub_source(s, trace))
             obj = os.path.join(tmp, s[:-4] + tag + ".o")
-            jobs_list.append(([hipcc] + flags + ({"_trace": ["-DREX_TU_TRACE=1"], "_seg": ["-DREX_TU_SEG=1"], "_pol": ["-DREX_TU_POL=1"], "_rnn": ["-DREX_TU_RNN=1"]}.get(trace, [])) + ["-c", src, "-o", obj], obj))
+            jobs_list.append(([hipcc] + flags + TAG_DEFINES.get(trace, []) + ["-c", src, "-o", obj], obj))
 
         def run(job):
             if verbose:

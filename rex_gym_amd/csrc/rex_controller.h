@@ -199,9 +199,28 @@ __device__ __forceinline__ void gait_loop_leg(GaitState& g, int mode, float v, f
   gait_frame(mine, own, v, angle, direction, rot, frame);
 }
 
-// model/motor.py:76-143 (position-control branch, strength ratio 1).  Divisions by the constants R and 10
+// model/motor.py:76-143 (position-control branch).  Divisions by the constants R and 10
 // are written as multiplications by their reciprocals (1 ulp from the numpy result, far inside the 1e-5 N m
 // parity tolerance) -- an IEEE fp32 division is a ~15-instruction sequence on gfx950.
+// The actuator's knobs (motor.py:40-74): battery voltage, viscous damping and the strength ratio, next to the PD gains.
+// The nominal motor is (32 V, 0, 1): x + 0 and x * 1 are exact, so its torques are those of the constants written out.
+constexpr float kMotorVoltage = 32.0f;   // MOTOR_VOLTAGE, motor.py:11
+__device__ __forceinline__ void motor_torque(float cmd, float q, float qd, float qd_true, float kp, float kd, float voltage, float damping,
+                                             float strength, float& actual, float& observed) {
+  constexpr float RINV = 1.0f / 0.186f, KT = 0.0954f;
+  float pwm = -1.0f * kp * (q - cmd) - kd * qd;
+  pwm = __builtin_amdgcn_fmed3f(pwm, -1.0f, 1.0f);
+  observed = __builtin_amdgcn_fmed3f(KT * (pwm * voltage * RINV), -5.7f, 5.7f);                                  // motor.py:116-119
+  const float vnet = __builtin_amdgcn_fmed3f(pwm * voltage - (KT + damping) * qd_true, -50.0f, 50.0f);           // motor.py:123-126
+  const float cur = vnet * RINV;
+  const float mag = fabsf(cur);
+  // np.interp(|I|, [0,10,...,60], [0,1,1.9,2.45,3.0,3.25,3.5]), clamped at the ends.  The table is concave (slopes
+  // 0.1, 0.09, 0.055, 0.055, 0.025, 0.025), so the interpolant is the minimum of its segment lines and the end
+  // clamp: branch-free, where a per-segment select compiles to a switch tree per motor.
+  const float t = fminf(fminf(fminf(0.1f * mag, fmaf(0.09f, mag, 0.1f)), fminf(fmaf(0.055f, mag, 0.8f), fmaf(0.025f, mag, 2.0f))), 3.5f);
+  actual = strength * copysignf(t, cur);                                                                         // motor.py:141
+}
+// ... and the nominal motor (32 V, no damping, strength ratio 1) as the kernels without per-env parameters have always had it
 __device__ __forceinline__ void motor_torque(float cmd, float q, float qd, float qd_true, float kp, float kd,
                                              float& actual, float& observed) {
   constexpr float V = 32.0f, RINV = 1.0f / 0.186f, KT = 0.0954f;
@@ -211,9 +230,6 @@ __device__ __forceinline__ void motor_torque(float cmd, float q, float qd, float
   const float vnet = __builtin_amdgcn_fmed3f(pwm * V - (KT + 0.0f) * qd_true, -50.0f, 50.0f);
   const float cur = vnet * RINV;
   const float mag = fabsf(cur);
-  // np.interp(|I|, [0,10,...,60], [0,1,1.9,2.45,3.0,3.25,3.5]), clamped at the ends.  The table is concave (slopes
-  // 0.1, 0.09, 0.055, 0.055, 0.025, 0.025), so the interpolant is the minimum of its segment lines and the end
-  // clamp: branch-free, where a per-segment select compiles to a switch tree per motor.
   const float t = fminf(fminf(fminf(0.1f * mag, fmaf(0.09f, mag, 0.1f)), fminf(fmaf(0.055f, mag, 0.8f), fmaf(0.025f, mag, 2.0f))), 3.5f);
   actual = copysignf(t, cur);
 }

@@ -11,6 +11,7 @@
 //   rex_reset_kernel    snapshot restore + per-episode draws (walk_env.py:125-154).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <type_traits>
 #include <stdint.h>
 #include <stdio.h>
 #include <string.h>
@@ -285,6 +286,13 @@ struct DevCfg {
   float anchor;              // on_rack: rex::kRackAnchor, else 0
   float obs_hi_ang, obs_hi_rate;
 };
+// the actuator's per-env knobs (rex_set_motor_params / rex_set_motor_randomization; MotorModel's setters, motor.py:40-74): an argument of
+// the MOTOR instantiations of the step kernel alone (StepArg below) -- DevCfg and the other kernels' arguments are what they were
+struct MotDev {
+  const float* params;        // [4 + NM][n] word-major: voltage, viscous damping, kp, kd, strength ratio of every motor (nullptr: 32, 0, kp, kd, 1)
+  float lo[5], hi[5];         // per-reset ranges of strength, voltage, damping, kp, kd (hi == 0: that quantity is not drawn)
+  int32_t on, per_motor;      // any of them drawn; one strength draw per motor (else one per env)
+};
 
 // per-task constants of the reference env classes (walk_env.py:34-40,104-114, gallop_env.py:45-53,
 // 119-130, turn_env.py:33-39,100-110, poses_env.py:38-44,115-117, standup_env.py:32-38,99-101)
@@ -390,6 +398,56 @@ __device__ __forceinline__ Ground env_ground(const DevCfg& c, int i, int gidx, i
   return g;
 }
 
+// ---- the actuator of env i in its current episode ----
+// Explicit entries (rex_set_motor_params) first, then the per-reset draws on top: as the mass / friction draws of env_ground a pure
+// function of (seed, global env index, episode), so nothing is stored and every substep of the episode forms the same numbers again.
+// Philox blocks (counter word 2) 3 -- voltage, damping, kp, kd -- and 4 + (j >> 2) -- the strength of motor j, word j & 3; one
+// draw per env: block 4, word 0 --: behind env_reset (0), env_ground (1) and mixed_task_of (2), in front of the sensor noise (16 ...).
+enum { kMrStrength = 0, kMrVoltage = 1, kMrDamping = 2, kMrKp = 3, kMrKd = 4 };
+struct MotorScalars { float voltage, damping, kp, kd; };
+__host__ __device__ __forceinline__ bool motor_params_on(const MotDev& m) { return m.params != nullptr || m.on != 0; }
+__device__ __forceinline__ float mr_draw(const MotDev& m, int q, uint32_t w) { return fmaf(m.hi[q] - m.lo[q], u01(w), m.lo[q]); }
+__device__ __forceinline__ MotorScalars motor_scalars(const DevCfg& c, const MotDev& m, int i, int gidx, int episode) {
+  MotorScalars r{kMotorVoltage, 0.0f, c.kp, c.kd};
+  if (m.params) {
+    r.voltage = m.params[i]; r.damping = m.params[(size_t)c.n + i];
+    r.kp = m.params[2 * (size_t)c.n + i]; r.kd = m.params[3 * (size_t)c.n + i];
+  }
+  if (m.hi[kMrVoltage] > 0.0f || m.hi[kMrDamping] > 0.0f || m.hi[kMrKp] > 0.0f || m.hi[kMrKd] > 0.0f) {
+    uint32_t ctr[4] = {(uint32_t)episode, (uint32_t)gidx, 3u, 0u};
+    philox4x32(ctr, c.seed_lo, c.seed_hi);
+    if (m.hi[kMrVoltage] > 0.0f) r.voltage = mr_draw(m, kMrVoltage, ctr[0]);
+    if (m.hi[kMrDamping] > 0.0f) r.damping = mr_draw(m, kMrDamping, ctr[1]);
+    if (m.hi[kMrKp] > 0.0f) r.kp = mr_draw(m, kMrKp, ctr[2]);
+    if (m.hi[kMrKd] > 0.0f) r.kd = mr_draw(m, kMrKd, ctr[3]);
+  }
+  return r;
+}
+// strength ratios of motors j0 .. j0 + COUNT - 1 (ascending: a Philox block serves four neighbours)
+template <int COUNT>
+__device__ __forceinline__ void motor_strengths(const DevCfg& c, const MotDev& m, int i, int gidx, int episode, int j0, float* out) {
+#pragma unroll
+  for (int k = 0; k < COUNT; ++k) out[k] = m.params ? m.params[(size_t)(4 + j0 + k) * c.n + i] : 1.0f;
+  if (m.hi[kMrStrength] > 0.0f) {
+    uint32_t ctr[4];
+    int have = -1;
+#pragma unroll
+    for (int k = 0; k < COUNT; ++k) {
+      const int j = m.per_motor ? j0 + k : 0, b = j >> 2, w = j & 3;
+      if (b != have) {
+        ctr[0] = (uint32_t)episode; ctr[1] = (uint32_t)gidx; ctr[2] = 4u + (uint32_t)b; ctr[3] = 0u;
+        philox4x32(ctr, c.seed_lo, c.seed_hi);
+        have = b;
+      }
+      out[k] = mr_draw(m, kMrStrength, w == 0 ? ctr[0] : (w == 1 ? ctr[1] : (w == 2 ? ctr[2] : ctr[3])));
+    }
+  }
+}
+// what the MOTOR instantiations receive behind the policy argument: the actor's (or nothing), then the actuator's knobs
+template <class P> struct WithMot : P { MotDev mot; };
+template <bool POLICY, bool RNN, bool MOTOR> struct StepArg { using type = typename PolArg<POLICY, RNN>::type; };
+template <bool POLICY, bool RNN> struct StepArg<POLICY, RNN, true> { using type = WithMot<typename PolArg<POLICY, RNN>::type>; };
+
 // Rex.ReceiveObservation (rex.py:726-733): the true observation goes to the front of the history ring.  `owner`: this
 // lane writes the words of its leg's motors; `live` (one lane per env): the arm's, the base quaternion and angular velocity.
 template <int NM, int NL, bool ARM>
@@ -422,15 +480,30 @@ __device__ __forceinline__ void receive_observation(const DevCfg& c, EnvState& e
 }
 
 // Rex.ApplyAction + stepSimulation + ReceiveObservation (rex.py:158-163, 568-641) for the motors this lane carries.
-template <bool LANECAP, bool TRACE, int NL, bool ARM, class SM, class ARMP>
+// MOTOR: the instantiations that read the per-env actuator parameters (rex_set_motor_params / rex_set_motor_randomization) -- kept
+// apart (-DREX_TU_MOT=1, launcher names _mseg / _mpol / _mrnn) so that the product kernels stay exactly what they were.
+template <bool LANECAP, bool TRACE, bool MOTOR, int NL, bool ARM, class SM, class ARMP>
 __device__ __forceinline__ void rex_substep(const DevCfg& c, EnvState& e, int i, bool live, bool owner, int leg0, MotorSide<NL, ARM>& ms,
-                                            const SM& sm, const Ground& ground, ARMP& armp) {
+                                            const SM& sm, const Ground& ground, ARMP& armp, const MotDev* mot = nullptr) {
   constexpr int NM = ARMP::NM, N = MotorSide<NL, ARM>::N;
   float tau[N];
   const float limit = 1.0f / c.dt;  // OVERHEAT_SHUTDOWN_TIME / time_step, rex.py:607
   int s0 = 0, s1 = 0;
   float alpha = 0.0f;
   if (c.hist) delay_slots(e.hist, c.pd_latency, c.pd_slots, c.pd_alpha, s0, s1, alpha);   // what the PD loop sees: _GetPDObservation, rex.py:755-759
+  // the env's actuator: formed anew in every substep and dead before the solver sweeps -- the sweep loop carries none of it
+  MotorScalars mp{kMotorVoltage, 0.0f, c.kp, c.kd};
+  float strength[MOTOR ? N : 1];
+  if constexpr (MOTOR) {
+    // opaque copies of the env index and the episode: what is formed from them here is invariant over the substeps of a step, and
+    // would otherwise be hoisted in front of that loop and carried through every solver sweep
+    int io = i, ep = e.episode;
+    asm volatile("" : "+v"(io), "+v"(ep));
+    const int gidx = c.env_index_base + io;
+    mp = motor_scalars(c, *mot, io, gidx, ep);
+    motor_strengths<3 * NL>(c, *mot, io, gidx, ep, MotorSide<NL, ARM>::motor(leg0, 0), strength);
+    if constexpr (ARM) motor_strengths<6>(c, *mot, io, gidx, ep, 12, strength + 3 * NL);
+  }
 #pragma unroll
   for (int jl = 0; jl < N; ++jl) {
     const int j = MotorSide<NL, ARM>::motor(leg0, jl);
@@ -439,7 +512,8 @@ __device__ __forceinline__ void rex_substep(const DevCfg& c, EnvState& e, int i,
     float qo = qt, qdo = qdt;
     if (c.hist) { qo = delayed_word(c, i, s0, s1, alpha, j); qdo = delayed_word(c, i, s0, s1, alpha, NM + j); }
     float act, obs;
-    motor_torque(ms.cmd[jl], qo, qdo, qdt, c.kp, c.kd, act, obs);
+    if constexpr (MOTOR) motor_torque(ms.cmd[jl], qo, qdo, qdt, mp.kp, mp.kd, mp.voltage, mp.damping, strength[jl], act, obs);
+    else motor_torque(ms.cmd[jl], qo, qdo, qdt, c.kp, c.kd, act, obs);
     uint32_t cnt = ms.heat(jl);
     cnt = fabsf(act) > 2.45f ? min(cnt + 1u, 65535u) : 0u;                      // rex.py:603-606
     if ((float)cnt > limit) e.motor_en &= ~(1u << j);                           // rex.py:607-608 (lane groups: the lane's own bits;
@@ -864,11 +938,11 @@ __device__ __forceinline__ void gather_legs(const SM& sm, int leg0, EnvState& e,
 // and one-wave workgroups keep a multi-round launch (> 16 384 envs) from waiting for the slowest of four waves before a CU takes new work
 // (65 536 walk-IK envs, fused actor per step: 68.9 M env-steps/s with four-wave workgroups)
 #define REX_POLICY_WAVES(EPW) ((EPW) <= 8 ? 4 : 1)
-template <int EPW, bool ARM, bool MIXED, bool BODY, bool TRACE = false, bool SEG = false, bool POLICY = false, bool RNN = false>
+template <int EPW, bool ARM, bool MIXED, bool BODY, bool TRACE = false, bool SEG = false, bool POLICY = false, bool RNN = false, bool MOTOR = false>
 __global__ __launch_bounds__(POLICY && !RNN ? REX_WAVE * REX_POLICY_WAVES(EPW) : REX_WAVE) REX_STEP_KERNEL_ATTR void rex_step_kernel(DevCfg c, float* __restrict__ state, const float* __restrict__ snap,
                                                             const float* __restrict__ action0, float* __restrict__ obs_out0,
                                                             float* __restrict__ reward_out0, uint8_t* __restrict__ done_out0,
-                                                            float* __restrict__ cmd_out0, typename PolArg<POLICY, RNN>::type pol) {
+                                                            float* __restrict__ cmd_out0, typename StepArg<POLICY, RNN, MOTOR>::type pol) {
   // POLICY (the instantiations behind rex_step_policy / rex_step_segment_policy; the base and arm step units are compiled once more with
   // -DREX_TU_POL=1): a SEG kernel whose actions are not read from action0 but computed, step by step, by the reference's Gaussian MLP
   // actor on the observation the env returned last (rex_policy.h) -- a closed-loop rollout segment in one launch.  Their workgroup is
@@ -1154,7 +1228,9 @@ __global__ __launch_bounds__(POLICY && !RNN ? REX_WAVE * REX_POLICY_WAVES(EPW) :
   };
 
   // Rex.Step (a REX_TASK_MIXED wave runs one task: c_ is its wave-uniform view of the config)
-  for (int k = 0; k < c_.action_repeat; ++k) rex_substep<false, TRACE>(c_, e, i, live, owner, leg0, ms, sm, ground, armp);
+  const MotDev* mot = nullptr;
+  if constexpr (MOTOR) mot = &pol.mot;
+  for (int k = 0; k < c_.action_repeat; ++k) rex_substep<false, TRACE, MOTOR>(c_, e, i, live, owner, leg0, ms, sm, ground, armp, mot);
   REX_STAMP(t_substeps);
   epilogue(live, owner);
 #ifdef REX_PROF
@@ -1240,7 +1316,7 @@ __global__ __launch_bounds__(REX_WAVE) void rex_settle_kernel(DevCfg c, float* _
 #pragma unroll
         for (int jl = 0; jl < 3 * NL; ++jl) ms.cmd[jl] = reset_pose(c, leg_joint<NL>(leg0, jl));
       }
-      rex_substep<true, false>(cs, e, t, keeps, owner, leg0, ms, sm, ground, armp);
+      rex_substep<true, false, false>(cs, e, t, keeps, owner, leg0, ms, sm, ground, armp);   // (MOTOR = false: the reset motion is the nominal robot's)
     }
   }
   receive_observation<NM>(cs, e, t, keeps, owner, leg0, ms);                                                   // rex.py:323
@@ -1318,6 +1394,7 @@ struct RexSim {
   int mixed_blocks;
   int32_t* d_class;      // a regrouped mixed batch: task slot of every env (rexsim.hip, rex_regroup_mixed_*), and its regions
   rex::MixRegions mix_regions;
+  rex::MotDev mot;       // rex_set_motor_params / rex_set_motor_randomization: set -> the MOTOR instantiations are launched
   rex::PolDev pol;       // rex_set_policy: the actor of rex_step_policy / rex_step_segment_policy
   float* d_polbuf;       // the packed actor (library-owned; rex_policy.h policy_offsets) and its capacity in floats
   int polbuf_floats;
@@ -1325,7 +1402,7 @@ struct RexSim {
   float* d_rnn_state;     // the recurrent actor's GRU state [state_size][n]: caller-owned, live
   int rnn_state_size;
   bool use_policy;        // this launch runs the fused-actor kernels (set by step_launch)
-  int pol_attr_bytes;     // the dynamic-LDS limit this sim has already set on its fused-actor kernel (hipFuncSetAttribute)
+  int pol_attr_bytes[2];  // the dynamic-LDS limit this sim has already set on its fused-actor kernel (hipFuncSetAttribute): [0] the plain, [1] the MOTOR instantiation
   int pol_lds_bytes;      // dynamic LDS of the fused-actor kernels: the weights' copy (0: they do not fit next to four waves' rows and are streamed)
   // rex_render_set_visuals: one device allocation holding the BVH nodes [16 dwords each], the leaf-ordered triangles [9 floats],
   // and per visual instance its root node and mesh-frame root box [6 floats] (rex_render_mesh.hip); null until set
@@ -1356,6 +1433,15 @@ void rex_launch_step_base_pol(RexSim* s, int blocks, hipStream_t st, const float
 void rex_launch_step_arm_pol(RexSim* s, int blocks, hipStream_t st, const float* a, float* o, float* r, uint8_t* d, float* m);
 void rex_launch_step_base_rnn(RexSim* s, int blocks, hipStream_t st, const float* a, float* o, float* r, uint8_t* d, float* m);
 void rex_launch_step_arm_rnn(RexSim* s, int blocks, hipStream_t st, const float* a, float* o, float* r, uint8_t* d, float* m);
+void rex_launch_step_base_mseg(RexSim* s, int blocks, hipStream_t st, const float* a, float* o, float* r, uint8_t* d, float* m);
+void rex_launch_step_arm_mseg(RexSim* s, int blocks, hipStream_t st, const float* a, float* o, float* r, uint8_t* d, float* m);
+void rex_launch_step_mixed_base_mseg(RexSim* s, int blocks, hipStream_t st, const float* a, float* o, float* r, uint8_t* d, float* m);
+void rex_launch_step_mixed_arm_mseg(RexSim* s, int blocks, hipStream_t st, const float* a, float* o, float* r, uint8_t* d, float* m);
+void rex_launch_step_body_mseg(RexSim* s, int blocks, hipStream_t st, const float* a, float* o, float* r, uint8_t* d, float* m);
+void rex_launch_step_base_mpol(RexSim* s, int blocks, hipStream_t st, const float* a, float* o, float* r, uint8_t* d, float* m);
+void rex_launch_step_arm_mpol(RexSim* s, int blocks, hipStream_t st, const float* a, float* o, float* r, uint8_t* d, float* m);
+void rex_launch_step_base_mrnn(RexSim* s, int blocks, hipStream_t st, const float* a, float* o, float* r, uint8_t* d, float* m);
+void rex_launch_step_arm_mrnn(RexSim* s, int blocks, hipStream_t st, const float* a, float* o, float* r, uint8_t* d, float* m);
 void rex_launch_settle_base(RexSim* s, int nrec, hipStream_t st, float* snap);   // <false, *>
 void rex_launch_settle_arm(RexSim* s, int nrec, hipStream_t st, float* snap);    // <true, *>
 
@@ -1373,7 +1459,16 @@ void rex_launch_settle_arm(RexSim* s, int nrec, hipStream_t st, float* snap);   
 #ifndef REX_TU_RNN
 #define REX_TU_RNN 0      /* -DREX_TU_RNN=1: the recurrent fused-actor instantiations (rex_set_policy_recurrent; launcher names end in _rnn) */
 #endif
-#if REX_TU_TRACE
+#ifndef REX_TU_MOT
+#define REX_TU_MOT 0      /* -DREX_TU_MOT=1 next to _SEG, _POL or _RNN: the same instantiations with the per-env actuator parameters (MOTOR; launcher names _mseg, _mpol, _mrnn) */
+#endif
+#if REX_TU_MOT && REX_TU_SEG
+#define REX_STEP_LAUNCHER(group) rex_launch_step_##group##_mseg
+#elif REX_TU_MOT && REX_TU_POL
+#define REX_STEP_LAUNCHER(group) rex_launch_step_##group##_mpol
+#elif REX_TU_MOT && REX_TU_RNN
+#define REX_STEP_LAUNCHER(group) rex_launch_step_##group##_mrnn
+#elif REX_TU_TRACE
 #define REX_STEP_LAUNCHER(group) rex_launch_step_##group##_trace
 #elif REX_TU_SEG
 #define REX_STEP_LAUNCHER(group) rex_launch_step_##group##_seg
@@ -1384,35 +1479,42 @@ void rex_launch_settle_arm(RexSim* s, int nrec, hipStream_t st, float* snap);   
 #else
 #define REX_STEP_LAUNCHER(group) rex_launch_step_##group
 #endif
+// the last argument of a step launch: the actor's part (P = NoPol / PolDev / RnnDev), for the MOTOR instantiations with the actuator's knobs behind it
+template <bool MOTOR, class P>
+static typename std::conditional<MOTOR, rex::WithMot<P>, P>::type rex_step_arg(const RexSim* s, const P& pol) {
+  if constexpr (MOTOR) { rex::WithMot<P> w; static_cast<P&>(w) = pol; w.mot = s->mot; return w; }
+  else return pol;
+}
 // the fused-actor kernels: four one-wave blocks to a workgroup; the actor's weights in dynamic LDS where they fit (RexSim::pol_lds_bytes, rex_set_policy)
-template <int EPW, bool ARM>
+template <int EPW, bool ARM, bool MOTOR = false>
 static void rex_launch_policy_kernel(RexSim* s, int blocks, hipStream_t st, const float* a, float* o, float* r, uint8_t* d, float* m) {
-  auto kern = rex::rex_step_kernel<EPW, ARM, false, false, false, true, true>;
-  if (s->pol_lds_bytes > s->pol_attr_bytes) {      // (per sim, i.e. per device: the attribute belongs to the function on the current device)
+  auto kern = rex::rex_step_kernel<EPW, ARM, false, false, false, true, true, false, MOTOR>;
+  int& attr_bytes = s->pol_attr_bytes[MOTOR ? 1 : 0];   // (a sim launches either instantiation, as parameters are set and removed: one record each)
+  if (s->pol_lds_bytes > attr_bytes) {      // (per sim, i.e. per device: the attribute belongs to the function on the current device)
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, s->pol_lds_bytes);
-    s->pol_attr_bytes = s->pol_lds_bytes;
+    attr_bytes = s->pol_lds_bytes;
   }
   constexpr int W = REX_POLICY_WAVES(EPW);
   hipLaunchKernelGGL(kern, dim3((blocks + W - 1) / W), dim3(REX_WAVE * W), (size_t)s->pol_lds_bytes, st,
-                     s->dev, s->d_state, s->d_snap, a, o, r, d, m, s->pol);
+                     s->dev, s->d_state, s->d_snap, a, o, r, d, m, rex_step_arg<MOTOR>(s, s->pol));
 }
 // the recurrent fused-actor kernels: one-wave workgroups, no dynamic LDS (the weights are streamed)
-template <int EPW, bool ARM>
+template <int EPW, bool ARM, bool MOTOR = false>
 static void rex_launch_rnn_kernel(RexSim* s, int blocks, hipStream_t st, const float* a, float* o, float* r, uint8_t* d, float* m) {
   rex::RnnDev pol;
   static_cast<rex::PolDev&>(pol) = s->pol;
   pol.state = s->d_rnn_state;
-  hipLaunchKernelGGL((rex::rex_step_kernel<EPW, ARM, false, false, false, true, true, true>), dim3(blocks), dim3(REX_WAVE), 0, st,
-                     s->dev, s->d_state, s->d_snap, a, o, r, d, m, pol);
+  hipLaunchKernelGGL((rex::rex_step_kernel<EPW, ARM, false, false, false, true, true, true, MOTOR>), dim3(blocks), dim3(REX_WAVE), 0, st,
+                     s->dev, s->d_state, s->d_snap, a, o, r, d, m, rex_step_arg<MOTOR>(s, pol));
 }
 #if REX_TU_POL
-#define REX_LAUNCH_STEP(EPW, ARM, MIXED, BODY) rex_launch_policy_kernel<EPW, ARM>(s, blocks, st, a, o, r, d, m)
+#define REX_LAUNCH_STEP(EPW, ARM, MIXED, BODY) rex_launch_policy_kernel<EPW, ARM, REX_TU_MOT != 0>(s, blocks, st, a, o, r, d, m)
 #elif REX_TU_RNN
-#define REX_LAUNCH_STEP(EPW, ARM, MIXED, BODY) rex_launch_rnn_kernel<EPW, ARM>(s, blocks, st, a, o, r, d, m)
+#define REX_LAUNCH_STEP(EPW, ARM, MIXED, BODY) rex_launch_rnn_kernel<EPW, ARM, REX_TU_MOT != 0>(s, blocks, st, a, o, r, d, m)
 #else
 #define REX_LAUNCH_STEP(EPW, ARM, MIXED, BODY)                                                                                  \
-  hipLaunchKernelGGL((rex::rex_step_kernel<EPW, ARM, MIXED, BODY, REX_TU_TRACE != 0, REX_TU_SEG != 0, false>), dim3(blocks), dim3(REX_WAVE), 0, st, s->dev, s->d_state, s->d_snap, \
-                     a, o, r, d, m, rex::NoPol{})
+  hipLaunchKernelGGL((rex::rex_step_kernel<EPW, ARM, MIXED, BODY, REX_TU_TRACE != 0, REX_TU_SEG != 0, false, false, REX_TU_MOT != 0>), dim3(blocks), dim3(REX_WAVE), 0, st, s->dev, s->d_state, s->d_snap, \
+                     a, o, r, d, m, rex_step_arg<REX_TU_MOT != 0>(s, rex::NoPol{}))
 #endif
 #define REX_LAUNCH_BY_EPW(ARM, MIXED, BODY)                                           \
   do {                                                                                \

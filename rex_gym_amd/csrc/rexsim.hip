@@ -207,6 +207,31 @@ __global__ void rex_motor_kernel(int n, const float* __restrict__ cmd, const flo
   actual[i] = a; observed[i] = o;
 }
 
+__global__ void rex_motor_params_kernel(int n, const float* __restrict__ cmd, const float* __restrict__ q, const float* __restrict__ qd,
+                                        const float* __restrict__ qdt, const float* __restrict__ par, float* __restrict__ actual,
+                                        float* __restrict__ observed) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  float a, o;
+  motor_torque(cmd[i], q[i], qd[i], qdt[i], par[5 * (size_t)i], par[5 * (size_t)i + 1], par[5 * (size_t)i + 2], par[5 * (size_t)i + 3],
+               par[5 * (size_t)i + 4], a, o);
+  actual[i] = a; observed[i] = o;
+}
+
+// rex_get_motor_params: what rex_substep forms for env i in its current episode, all rows
+template <int NM>
+__global__ void rex_get_motor_params_kernel(DevCfg c, MotDev mot, const float* __restrict__ state, float* __restrict__ out) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= c.n) return;
+  const int gidx = c.env_index_base + i, episode = (int)ldi(state, c.n, Lay<NM>::EPISODE, i);
+  const MotorScalars m = motor_scalars(c, mot, i, gidx, episode);
+  float st[NM];
+  motor_strengths<NM>(c, mot, i, gidx, episode, 0, st);
+  out[i] = m.voltage; out[(size_t)c.n + i] = m.damping; out[2 * (size_t)c.n + i] = m.kp; out[3 * (size_t)c.n + i] = m.kd;
+#pragma unroll
+  for (int j = 0; j < NM; ++j) out[(size_t)(4 + j) * c.n + i] = st[j];
+}
+
 __global__ void rex_gait_kernel(int n, int mode, double* __restrict__ planner, const double* __restrict__ params,
                                 float* __restrict__ frames) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -501,6 +526,8 @@ int rex_create(const RexConfig* cfg, int device, float* d_state, void* stream, R
   d.pose_index = cfg->pose_index; d.pose_value = cfg->pose_value;
   d.range_normalize = cfg->range_normalize;
   d.terrain = nullptr; d.terrain_mid = nullptr; d.n_terrain = 0; d.body_params = nullptr;
+  s->mot.params = nullptr; s->mot.on = 0; s->mot.per_motor = 1;
+  for (int k = 0; k < 5; ++k) { s->mot.lo[k] = 0.0f; s->mot.hi[k] = 0.0f; }
   d.perm = nullptr; d.sweeps = nullptr; s->d_perm = nullptr; s->d_sweeps = nullptr; s->d_regroup = nullptr; d.clock = nullptr; s->d_clock = nullptr; s->h_clock = nullptr;
   d.geo = rex::HfGeom{256, 20.0f, 20.0f, 127.5f, 127.5f, 254.999f, 254.999f}; d.hf_stride = 65536;   /* model/terrain.py:32-54 */
   d.init_z = cfg->init_height > 0.0f ? cfg->init_height : rex::kInitZ;
@@ -660,6 +687,8 @@ int rex_set_history(RexSim* s, float* d_history) {
 
 int rex_set_event_trace(RexSim* s, uint32_t* d_trace) {
   if (!s) return fail(REX_EINVAL, "rex_set_event_trace: null sim%s", "");
+  if (d_trace && rex::motor_params_on(s->mot))
+    return fail(REX_EINVAL, "rex_set_event_trace: the event trace (a debug aid of the nominal robot) is not offered together with motor parameters%s", "");
   s->dev.trace = d_trace;
   return REX_OK;
 }
@@ -667,6 +696,49 @@ int rex_set_event_trace(RexSim* s, uint32_t* d_trace) {
 int rex_set_body_params(RexSim* s, const float* d_params) {
   if (!s) return fail(REX_EINVAL, "rex_set_body_params: null sim%s", "");
   s->dev.body_params = d_params;
+  return REX_OK;
+}
+
+int rex_set_motor_params(RexSim* s, const float* d_params) {
+  if (!s) return fail(REX_EINVAL, "rex_set_motor_params: null sim%s", "");
+  if (d_params && s->dev.trace) return fail(REX_EINVAL, "rex_set_motor_params: motor parameters are not offered together with the event trace%s", "");
+  s->mot.params = d_params;
+  return REX_OK;
+}
+
+int rex_set_motor_randomization(RexSim* s, const RexMotorRandom* r) {
+  if (!s) return fail(REX_EINVAL, "rex_set_motor_randomization: null sim%s", "");
+  rex::MotDev& d = s->mot;
+  if (!r) {
+    for (int k = 0; k < 5; ++k) { d.lo[k] = 0.0f; d.hi[k] = 0.0f; }
+    d.on = 0; d.per_motor = 1;
+    return REX_OK;
+  }
+  static const char* const names[5] = {"strength", "voltage", "damping", "kp", "kd"};
+  const float lo[5] = {r->strength_lo, r->voltage_lo, r->damping_lo, r->kp_lo, r->kd_lo};
+  const float hi[5] = {r->strength_hi, r->voltage_hi, r->damping_hi, r->kp_hi, r->kd_hi};
+  for (int k = 0; k < 5; ++k) {   // (written so that a NaN fails: every comparison with one is false)
+    if (!(lo[k] >= 0.0f && hi[k] >= lo[k] && hi[k] <= 3.0e38f))
+      return fail(REX_EINVAL, "rex_set_motor_randomization: the %s range must satisfy 0 <= lo <= hi (finite)", names[k]);
+  }
+  if (r->strength_per_motor != 0 && r->strength_per_motor != 1)
+    return fail(REX_EINVAL, "rex_set_motor_randomization: strength_per_motor must be 0 or 1%s", "");
+  if (s->dev.trace) return fail(REX_EINVAL, "rex_set_motor_randomization: motor parameters are not offered together with the event trace%s", "");
+  d.on = 0;
+  for (int k = 0; k < 5; ++k) { d.lo[k] = lo[k]; d.hi[k] = hi[k]; if (hi[k] > 0.0f) d.on = 1; }
+  d.per_motor = r->strength_per_motor;
+  return REX_OK;
+}
+
+int rex_get_motor_params(RexSim* s, float* d_out, void* stream) {
+  if (!s || !d_out) return fail(REX_EINVAL, "rex_get_motor_params: null %s", !s ? "sim" : "output buffer");
+  HIPCHK(hipSetDevice(s->device));
+  const int n = s->dev.n;
+  if (s->cfg.mark == REX_MARK_ARM)
+    hipLaunchKernelGGL(rex::rex_get_motor_params_kernel<18>, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, s->dev, s->mot, s->d_state, d_out);
+  else
+    hipLaunchKernelGGL(rex::rex_get_motor_params_kernel<12>, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, s->dev, s->mot, s->d_state, d_out);
+  HIPCHK(hipGetLastError());
   return REX_OK;
 }
 
@@ -847,6 +919,8 @@ int rex_step_segment_policy(RexSim* s, int num_steps, const float* d_obs_in, flo
 
 static int step_launch(RexSim* s, int num_steps, const float* d_action, float* d_obs, float* d_reward, uint8_t* d_done, float* d_motor_cmd, void* stream) {
   HIPCHK(hipSetDevice(s->device));
+  if (s->dev.trace && rex::motor_params_on(s->mot))
+    return fail(REX_EINVAL, "the event trace (a debug aid of the nominal robot) is not offered together with motor parameters%s", "");
   s->use_policy = num_steps < 0;
   if (num_steps < 0) num_steps = -num_steps;
   s->dev.nsteps = num_steps;
@@ -1107,6 +1181,16 @@ int rex_motor_torque(int n, const float* d_cmd, const float* d_q, const float* d
   return REX_OK;
 }
 
+int rex_motor_torque_params(int n, const float* d_cmd, const float* d_q, const float* d_qd, const float* d_qd_true, const float* d_par,
+                            float* d_actual, float* d_observed, void* stream) {
+  if (n <= 0 || !d_cmd || !d_q || !d_qd || !d_qd_true || !d_par || !d_actual || !d_observed)
+    return fail(REX_EINVAL, "rex_motor_torque_params: bad arguments%s", "");
+  hipLaunchKernelGGL(rex::rex_motor_params_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, n, d_cmd, d_q, d_qd, d_qd_true,
+                     d_par, d_actual, d_observed);
+  HIPCHK(hipGetLastError());
+  return REX_OK;
+}
+
 int rex_gait_loop(int n, int mode, double* d_planner, const double* d_params, float* d_frames_out, void* stream) {
   if (n <= 0 || (mode != 0 && mode != 1) || !d_planner || !d_params || !d_frames_out) return fail(REX_EINVAL, "rex_gait_loop: bad arguments%s", "");
   hipLaunchKernelGGL(rex::rex_gait_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, n, mode, d_planner, d_params, d_frames_out);
@@ -1150,6 +1234,17 @@ static void launch_step(RexSim* s, int blocks, hipStream_t st, const float* a, f
     else if (s->cfg.body_contacts) rex_launch_step_body_trace(s, blocks, st, a, o, r, d, m);
     else if (arm) rex_launch_step_arm_trace(s, blocks, st, a, o, r, d, m);
     else rex_launch_step_base_trace(s, blocks, st, a, o, r, d, m);
+    return;
+  }
+  if (rex::motor_params_on(s->mot)) {   // rex_set_motor_params / rex_set_motor_randomization: the segment instantiations that read the actuator's knobs
+    if (s->use_policy) {                // (rex_step is a segment of one step: the same arithmetic, bit for bit)
+      if (s->have_policy == 2) { if (arm) rex_launch_step_arm_mrnn(s, blocks, st, a, o, r, d, m); else rex_launch_step_base_mrnn(s, blocks, st, a, o, r, d, m); }
+      else if (arm) rex_launch_step_arm_mpol(s, blocks, st, a, o, r, d, m); else rex_launch_step_base_mpol(s, blocks, st, a, o, r, d, m);
+    }
+    else if (s->cfg.task == REX_TASK_MIXED) { if (arm) rex_launch_step_mixed_arm_mseg(s, blocks, st, a, o, r, d, m); else rex_launch_step_mixed_base_mseg(s, blocks, st, a, o, r, d, m); }
+    else if (s->cfg.body_contacts) rex_launch_step_body_mseg(s, blocks, st, a, o, r, d, m);
+    else if (arm) rex_launch_step_arm_mseg(s, blocks, st, a, o, r, d, m);
+    else rex_launch_step_base_mseg(s, blocks, st, a, o, r, d, m);
     return;
   }
   if (s->use_policy) {       // rex_step_policy / rex_step_segment_policy: the segment kernels with the actor in front of every step

@@ -81,7 +81,9 @@ class RexBatchEnv:
                  distance_weight=None, energy_weight=None, drift_weight=None, shake_weight=None,
                  tasks=None, mass_scale_range=None, friction_range=None, observation_noise_stdev=None,
                  heightfield=None, heightfield_cell=None, heightfield_origin=(0.0, 0.0, 0.0), init_height=None,
-                 body_contacts=None, on_rack=False, env_randomizer=None, forward_reward_cap=None, use_angle_in_observation=True, **ignored):
+                 body_contacts=None, on_rack=False, env_randomizer=None, forward_reward_cap=None, use_angle_in_observation=True,
+                 motor_strength_range=None, battery_voltage_range=None, motor_damping_range=None, motor_kp_range=None,
+                 motor_kd_range=None, motor_strength_per_motor=True, **ignored):
         import torch
         # Reference constructor keywords that only touch the GUI, logging or debugging are accepted and ignored; anything
         # else that would change what the env computes is an error here, not a silent no-op.
@@ -96,7 +98,24 @@ class RexBatchEnv:
                                  else [env_randomizer])
         if self._env_randomizers and auto_reset:
             raise ValueError("env_randomizer hooks run on the host inside reset(); with auto_reset the resets happen inside the "
-                             "launch -- use mass_scale_range / friction_range (per-reset draws in the kernel) instead")
+                             "launch -- use mass_scale_range / friction_range and the motor_*_range / battery_voltage_range "
+                             "keywords (per-reset draws in the kernel) instead")
+        # per-reset draws of the actuator's knobs inside the launch (rex_set_motor_randomization): (lo, hi) each, None: not drawn
+        motor_random = _lib.RexMotorRandom()
+        motor_random.strength_per_motor = int(bool(motor_strength_per_motor))
+        for name, rng in (("strength", motor_strength_range), ("voltage", battery_voltage_range), ("damping", motor_damping_range),
+                          ("kp", motor_kp_range), ("kd", motor_kd_range)):
+            if rng is None:
+                continue
+            try:
+                lo, hi = (float(v) for v in rng)
+            except (TypeError, ValueError):
+                raise ValueError(f"the {name} range must be a pair (lo, hi)") from None
+            if not (0.0 <= lo <= hi < float("inf")):     # (false for NaN as well)
+                raise ValueError(f"the {name} range must satisfy 0 <= lo <= hi (finite), got ({lo}, {hi})")
+            setattr(motor_random, name + "_lo", lo); setattr(motor_random, name + "_hi", hi)
+        self._motor_random = motor_random if any(r is not None for r in (motor_strength_range, battery_voltage_range, motor_damping_range,
+                                                                         motor_kp_range, motor_kd_range)) else None
         self._randomize_indices = None
         if terrain_type in ("hills", "mounts", "maze") and heightfield is None:
             raise NotImplementedError(
@@ -220,6 +239,9 @@ class RexBatchEnv:
                                           self._stream_ptr(), ctypes.byref(handle)), "rex_create")
         self._h = handle
         self._own_out = StepOut(self._obs, self._reward, self._done, torch)
+        self.motor_params_tensor = None
+        if self._motor_random is not None:
+            _lib.check(self._L.rex_set_motor_randomization(self._h, ctypes.byref(self._motor_random)), "rex_set_motor_randomization")
         self._p_cmd, self._info = self._cmd.data_ptr(), {"action": self._cmd}
         self._needs_reset = True
         from .rex_knobs import RexKnobs
@@ -338,6 +360,34 @@ class RexBatchEnv:
             if v is not None:
                 self.body_params[row] = torch.as_tensor(v, dtype=torch.float32, device=self.device)
         return self.body_params
+
+    def set_motor_params(self, voltage=None, damping=None, kp=None, kd=None, strength=None):
+        """Per-env actuator parameters (the knobs of the reference's MotorModel, model/motor.py:40-74, and the PD gains of
+        Rex.ApplyAction). Each argument: None (keep), a float, or an [N] tensor/array; strength also [num_motors, N] (one ratio
+        per motor, mark_constants order). The values live in the returned [4 + num_motors, N] device tensor -- rows voltage,
+        viscous damping, kp, kd, then the strength ratios -- which starts nominal (32 V, 0, motor_kp, motor_kd, 1) and may be
+        edited in place between steps. The reset motion stays the nominal robot's, as with set_body_params."""
+        torch = self._torch
+        if self.motor_params_tensor is None:
+            nominal = [32.0, 0.0, float(self.config.motor_kp), float(self.config.motor_kd)] + [1.0] * self.num_motors
+            table = torch.tensor(nominal, dtype=torch.float32, device=self.device)[:, None].repeat(1, self.num_envs).contiguous()
+            _lib.check(self._L.rex_set_motor_params(self._h, table.data_ptr()), "rex_set_motor_params")
+            self.motor_params_tensor = table
+        p = self.motor_params_tensor
+        for row, v in enumerate((voltage, damping, kp, kd)):
+            if v is not None:
+                p[row] = torch.as_tensor(v, dtype=torch.float32, device=self.device)
+        if strength is not None:
+            p[4:] = torch.as_tensor(strength, dtype=torch.float32, device=self.device)
+        return p
+
+    def motor_params(self):
+        """The actuator parameters in effect for every env's current episode -- explicit entries and per-reset draws -- as a new
+        [4 + num_motors, N] device tensor (rex_get_motor_params; rows as in set_motor_params)."""
+        torch = self._torch
+        out = torch.empty((4 + self.num_motors, self.num_envs), dtype=torch.float32, device=self.device)
+        _lib.check(self._L.rex_get_motor_params(self._h, out.data_ptr(), self._stream_ptr()), "rex_get_motor_params")
+        return out
 
     # ---- Gym / BatchEnv surface ----
     def reset(self, indices=None):
