@@ -2,12 +2,12 @@
 
 The library is compiled variant group by variant group -- one translation unit per group of rex_step_kernel /
 rex_settle_kernel instantiations (csrc/rex_step_*.hip, rex_settle_*.hip) next to the C ABI (csrc/rexsim.hip) -- in
-parallel, then linked (36 jobs: the step units are compiled four times, base and arm four times more, see TRACE_SOURCES ... MOT_SOURCES) where the single translation
+parallel, then linked (33 jobs, see variant_jobs(): every step unit once per mode it offers) where the single translation
 unit took over 2 minutes.
 
 Developer knobs (never needed for the product build):
   REX_LIB_PATH=<path>     write / load the library somewhere else (A/B builds)
-  REX_BUILD_ONLY=base,arm compile only these variant groups' kernels; the other launchers become stubs that report an error
+  REX_BUILD_ONLY=base,arm compile only these variant groups' kernels; launching another group's is an error return (REX_EINVAL)
   build(defines=[...], unity=True)  one translation unit (tools/prof_sections.py: -DREX_PROF keeps its counters in one
                           device global)
 """
@@ -20,29 +20,37 @@ from concurrent.futures import ThreadPoolExecutor
 PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(PKG_DIR, "csrc")
 LIB_PATH = os.environ.get("REX_LIB_PATH") or os.path.join(PKG_DIR, "librexsim_hip.so")   # REX_LIB_PATH: developer A/B builds
-# translation unit -> variant group name (REX_BUILD_ONLY) ; rexsim.hip (C ABI, reset and controller kernels) is always built
-GROUPS = {"rex_step_base.hip": "base", "rex_step_arm.hip": "arm", "rex_step_mixed_base.hip": "mixed_base",
-          "rex_step_mixed_arm.hip": "mixed_arm", "rex_step_body.hip": "body", "rex_settle_base.hip": "base", "rex_settle_arm.hip": "arm"}
-SOURCES = ["rexsim.hip", "rex_render.hip", "rex_render_mesh.hip"] + sorted(GROUPS)   # the renderers (rex_render, rex_render_visual): one kernel each, no variants
-# the step translation units are compiled a second time with -DREX_TU_TRACE=1: the kernel instantiations with the event trace
-# (rex_set_event_trace, a debug aid of the parity tests) compiled in -- the product kernels carry none of it
-TRACE_SOURCES = sorted(f for f in GROUPS if f.startswith("rex_step_"))
-# ... and a third time with -DREX_TU_SEG=1: the instantiations behind rex_step_segment (a loop over the steps of a rollout segment around
-# the step; kept apart because the loop costs registers -- what the body forms from loop invariants is hoisted -- and rex_step's own
-# kernels stay exactly what they were)
-SEG_SOURCES = TRACE_SOURCES
-# ... and the single-task toes-only units a fourth time with -DREX_TU_POL=1: the segment kernels with the reference's Gaussian MLP actor
-# evaluated in front of every step (rex_step_policy / rex_step_segment_policy, csrc/rex_policy.h)
-POL_SOURCES = ["rex_step_arm.hip", "rex_step_base.hip"]
-# ... and a fifth time with -DREX_TU_RNN=1: the same with the reference's RECURRENT actor (a GRU cell on a per-env state,
-# rex_set_policy_recurrent), kept apart so that the forward actor's kernels stay exactly what they were
-RNN_SOURCES = POL_SOURCES
-# ... and the segment, fused-actor and recurrent units once more with -DREX_TU_MOT=1: the same kernels reading the per-env actuator
-# parameters (rex_set_motor_params / rex_set_motor_randomization; rex_step runs them as a segment of one step), kept apart because the
-# parameter loads and draws cost registers: every other kernel stays exactly what it was
-MOT_SOURCES = [(s, "_mseg") for s in SEG_SOURCES] + [(s, "_mpol") for s in POL_SOURCES] + [(s, "_mrnn") for s in RNN_SOURCES]
-TAG_DEFINES = {"_trace": ["-DREX_TU_TRACE=1"], "_seg": ["-DREX_TU_SEG=1"], "_pol": ["-DREX_TU_POL=1"], "_rnn": ["-DREX_TU_RNN=1"],
-               "_mseg": ["-DREX_TU_SEG=1", "-DREX_TU_MOT=1"], "_mpol": ["-DREX_TU_POL=1", "-DREX_TU_MOT=1"], "_mrnn": ["-DREX_TU_RNN=1", "-DREX_TU_MOT=1"]}
+# variant group names in the order of csrc/rex_kernels.h RexStepGroup (REX_BUILD_ONLY; the bit numbers of -DREX_LEFT_OUT_GROUPS)
+GROUP_NAMES = ["base", "arm", "mixed_base", "mixed_arm", "body"]
+# translation unit -> variant group name; rexsim.hip (C ABI, launcher table, reset and controller kernels) is always built
+GROUPS = {**{"rex_step_%s.hip" % g: g for g in GROUP_NAMES}, "rex_settle_base.hip": "base", "rex_settle_arm.hip": "arm"}
+# (the renderers -- rex_render, rex_render_visual -- are one kernel each, no variants; rexsim.hip last: a unity build includes it behind the
+# units whose launchers its table names)
+SOURCES = sorted(GROUPS) + ["rex_render.hip", "rex_render_mesh.hip", "rexsim.hip"]
+# the modes a step unit is compiled in (csrc/rex_kernels.h RexStepMode, where the reason for each is recorded) and their object-file tags
+MODES = {"STEP": "", "TRACE": "_trace", "SEG": "_seg", "POL": "_pol", "RNN": "_rnn"}
+
+
+def variant_offered(group, mode, motor):
+    """csrc/rex_kernels.h rex_step_variant_offered: the fused actor in the single-task toes-only groups, the per-env actuator
+    parameters (MOTOR) in the segment-shaped modes."""
+    actor = mode in ("POL", "RNN")
+    return (not actor or group in ("base", "arm")) and (not motor or mode == "SEG" or actor)
+
+
+def variant_jobs():
+    """(source, object-file tag, defines) of every object of the library: the step units once per offered (mode, MOTOR), then the
+    settle units and the sources without variants."""
+    jobs = []
+    for motor in (False, True):
+        for mode, tag in MODES.items():
+            for g in GROUP_NAMES:
+                if variant_offered(g, mode, motor):
+                    defines = ([] if mode == "STEP" else ["-DREX_TU_MODE=REX_MODE_" + mode]) + (["-DREX_TU_MOT=1"] if motor else [])
+                    jobs.append(("rex_step_%s.hip" % g, ("_m" + tag[1:]) if motor else tag, defines))
+    return jobs + [(s, "", []) for s in SOURCES if not s.startswith("rex_step_")]
+
+
 HEADERS = sorted(f for f in os.listdir(CSRC) if f.endswith(".h"))   # every header the sources can include
 # -ffp-contract=on: a * b + c inside one expression is one fma and nothing else is fused -- the arithmetic of a kernel is fixed by its
 # source and does not depend on what else is compiled into it (hipcc's default lets the backend fuse across statements by heuristics:
@@ -62,7 +70,7 @@ def _hipcc():
 def _flags_stamp():
     # the compile flags fix the kernels' arithmetic (-ffp-contract=on): a flags-only edit of this file must rebuild too
     import hashlib
-    return hashlib.sha256(" ".join(HIPCC_FLAGS + POL_SOURCES + ["rnn"] + RNN_SOURCES + ["mot"] + [s + t for s, t in MOT_SOURCES]).encode()).hexdigest()[:16]
+    return hashlib.sha256(repr((HIPCC_FLAGS, variant_jobs())).encode()).hexdigest()[:16]
 
 
 def needs_build(lib_path=None):
@@ -86,23 +94,6 @@ def _stamp(lib_path, defines, only):
             f.write(_flags_stamp() + "\n")
 
 
-_STUB = """// stub of a variant group left out of a developer build (REX_BUILD_ONLY)
-#include "rex_kernels.h"
-#include <cstdio>
-#include <cstdlib>
-%s
-"""
-
-
-def _stub_source(tu, trace=False):
-    name = tu[:-4] + (trace if isinstance(trace, str) else ("_trace" if trace else ""))
-    if name.startswith("rex_step_"):
-        sig = "void rex_launch_%s(RexSim*, int, hipStream_t, const float*, float*, float*, uint8_t*, float*)" % name[4:]
-    else:
-        sig = "void rex_launch_%s(RexSim*, int, hipStream_t, float*)" % name[4:]
-    return _STUB % (sig + ' { fprintf(stderr, "librexsim_hip.so: variant group %s was left out of this developer build (REX_BUILD_ONLY)\\n"); abort(); }' % name)
-
-
 def build(force=False, verbose=False, lib_path=None, defines=(), unity=False, only=None, jobs=None):
     """Compile csrc/*.hip -> librexsim_hip.so. Returns the library path."""
     lib_path = lib_path or LIB_PATH
@@ -110,44 +101,18 @@ def build(force=False, verbose=False, lib_path=None, defines=(), unity=False, on
         return lib_path
     hipcc = _hipcc()
     only = only if only is not None else os.environ.get("REX_BUILD_ONLY")
-    keep = set(only.split(",")) if only else None
+    left_out = set(GROUP_NAMES) - set(only.split(",")) if only else set()
     flags = HIPCC_FLAGS + list(defines) + ["-I", CSRC]
+    if left_out:   # rexsim.hip's launcher table holds nullptr for these groups (step and settle): launching one is an error return
+        flags.append("-DREX_LEFT_OUT_GROUPS=%d" % sum(1 << GROUP_NAMES.index(g) for g in left_out))
+    todo = [j for j in variant_jobs() if GROUPS.get(j[0]) not in left_out]
     with tempfile.TemporaryDirectory(prefix="rexsim_build_") as tmp:
         if unity:
             uni = os.path.join(tmp, "unity.hip")
             with open(uni, "w") as f:
-                f.write("".join('#include "%s"\n' % os.path.join(CSRC, s) for s in SOURCES))
-                f.write("#undef REX_TU_TRACE\n#undef REX_STEP_LAUNCHER\n#undef REX_LAUNCH_STEP\n#define REX_TU_TRACE 1\n"
-                        "#define REX_STEP_LAUNCHER(group) rex_launch_step_##group##_trace\n"
-                        "#define REX_LAUNCH_STEP(EPW, ARM, MIXED, BODY) hipLaunchKernelGGL((rex::rex_step_kernel<EPW, ARM, MIXED, BODY, true>), "
-                        "dim3(blocks), dim3(REX_WAVE), 0, st, s->dev, s->d_state, s->d_snap, a, o, r, d, m, rex::NoPol{})\n")
-                f.write("".join('#include "%s"\n' % os.path.join(CSRC, s) for s in TRACE_SOURCES))
-                f.write("#undef REX_STEP_LAUNCHER\n#undef REX_LAUNCH_STEP\n"
-                        "#define REX_STEP_LAUNCHER(group) rex_launch_step_##group##_seg\n"
-                        "#define REX_LAUNCH_STEP(EPW, ARM, MIXED, BODY) hipLaunchKernelGGL((rex::rex_step_kernel<EPW, ARM, MIXED, BODY, false, true>), "
-                        "dim3(blocks), dim3(REX_WAVE), 0, st, s->dev, s->d_state, s->d_snap, a, o, r, d, m, rex::NoPol{})\n")
-                f.write("".join('#include "%s"\n' % os.path.join(CSRC, s) for s in SEG_SOURCES))
-                f.write("#undef REX_STEP_LAUNCHER\n#undef REX_LAUNCH_STEP\n#undef REX_TU_POL\n#define REX_TU_POL 1\n"
-                        "#define REX_STEP_LAUNCHER(group) rex_launch_step_##group##_pol\n"
-                        "#define REX_LAUNCH_STEP(EPW, ARM, MIXED, BODY) rex_launch_policy_kernel<EPW, ARM>(s, blocks, st, a, o, r, d, m)\n")
-                f.write("".join('#include "%s"\n' % os.path.join(CSRC, s) for s in POL_SOURCES))
-                f.write("#undef REX_STEP_LAUNCHER\n#undef REX_LAUNCH_STEP\n#undef REX_TU_POL\n#define REX_TU_POL 0\n#undef REX_TU_RNN\n#define REX_TU_RNN 1\n"
-                        "#define REX_STEP_LAUNCHER(group) rex_launch_step_##group##_rnn\n"
-                        "#define REX_LAUNCH_STEP(EPW, ARM, MIXED, BODY) rex_launch_rnn_kernel<EPW, ARM>(s, blocks, st, a, o, r, d, m)\n")
-                f.write("".join('#include "%s"\n' % os.path.join(CSRC, s) for s in RNN_SOURCES))
-                f.write("#undef REX_STEP_LAUNCHER\n#undef REX_LAUNCH_STEP\n#undef REX_TU_RNN\n#define REX_TU_RNN 0\n#undef REX_TU_MOT\n#define REX_TU_MOT 1\n"
-                        "#define REX_STEP_LAUNCHER(group) rex_launch_step_##group##_mseg\n"
-                        "#define REX_LAUNCH_STEP(EPW, ARM, MIXED, BODY) hipLaunchKernelGGL((rex::rex_step_kernel<EPW, ARM, MIXED, BODY, false, true, false, false, true>), "
-                        "dim3(blocks), dim3(REX_WAVE), 0, st, s->dev, s->d_state, s->d_snap, a, o, r, d, m, rex_step_arg<true>(s, rex::NoPol{}))\n")
-                f.write("".join('#include "%s"\n' % os.path.join(CSRC, s) for s in SEG_SOURCES))
-                f.write("#undef REX_STEP_LAUNCHER\n#undef REX_LAUNCH_STEP\n#undef REX_TU_POL\n#define REX_TU_POL 1\n"
-                        "#define REX_STEP_LAUNCHER(group) rex_launch_step_##group##_mpol\n"
-                        "#define REX_LAUNCH_STEP(EPW, ARM, MIXED, BODY) rex_launch_policy_kernel<EPW, ARM, true>(s, blocks, st, a, o, r, d, m)\n")
-                f.write("".join('#include "%s"\n' % os.path.join(CSRC, s) for s in POL_SOURCES))
-                f.write("#undef REX_STEP_LAUNCHER\n#undef REX_LAUNCH_STEP\n#undef REX_TU_POL\n#define REX_TU_POL 0\n#undef REX_TU_RNN\n#define REX_TU_RNN 1\n"
-                        "#define REX_STEP_LAUNCHER(group) rex_launch_step_##group##_mrnn\n"
-                        "#define REX_LAUNCH_STEP(EPW, ARM, MIXED, BODY) rex_launch_rnn_kernel<EPW, ARM, true>(s, blocks, st, a, o, r, d, m)\n")
-                f.write("".join('#include "%s"\n' % os.path.join(CSRC, s) for s in RNN_SOURCES))
+                for s, _, defs in todo:   # one explicit specialisation of rex_launch_step per inclusion: the template arguments tell them apart
+                    macros = {"REX_TU_MODE": "REX_MODE_STEP", "REX_TU_MOT": "0", **dict(d[2:].split("=") for d in defs)}
+                    f.write("".join("#undef %s\n#define %s %s\n" % (k, k, v) for k, v in macros.items()) + '#include "%s"\n' % os.path.join(CSRC, s))
             cmd = [hipcc] + flags + ["-shared", uni, "-o", lib_path]
             if verbose:
                 print(" ".join(cmd))
@@ -155,15 +120,9 @@ def build(force=False, verbose=False, lib_path=None, defines=(), unity=False, on
             _stamp(lib_path, defines, only)
             return lib_path
         jobs_list = []
-        for s, trace in [(s, "") for s in SOURCES] + [(s, "_trace") for s in TRACE_SOURCES] + [(s, "_seg") for s in SEG_SOURCES] + [(s, "_pol") for s in POL_SOURCES] + [(s, "_rnn") for s in RNN_SOURCES] + MOT_SOURCES:
-            src = os.path.join(CSRC, s)
-            tag = trace
-            if keep is not None and s in GROUPS and GROUPS[s] not in keep:
-                src = os.path.join(tmp, "stub_" + s[:-4] + tag + ".hip")
-                with open(src, "w") as f:
-                    f.write(_stub_source(s, trace))
+        for s, tag, defs in todo:
             obj = os.path.join(tmp, s[:-4] + tag + ".o")
-            jobs_list.append(([hipcc] + flags + TAG_DEFINES.get(trace, []) + ["-c", src, "-o", obj], obj))
+            jobs_list.append(([hipcc] + flags + defs + ["-c", os.path.join(CSRC, s), "-o", obj], obj))
 
         def run(job):
             if verbose:

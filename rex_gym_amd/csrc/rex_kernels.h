@@ -1413,109 +1413,74 @@ struct RexSim {
   float* d_vis_box;
 };
 
-// launchers, one per variant group (each in its own translation unit)
-void rex_launch_step_base(RexSim* s, int blocks, hipStream_t st, const float* a, float* o, float* r, uint8_t* d, float* m);
-void rex_launch_step_arm(RexSim* s, int blocks, hipStream_t st, const float* a, float* o, float* r, uint8_t* d, float* m);
-void rex_launch_step_mixed_base(RexSim* s, int blocks, hipStream_t st, const float* a, float* o, float* r, uint8_t* d, float* m);
-void rex_launch_step_mixed_arm(RexSim* s, int blocks, hipStream_t st, const float* a, float* o, float* r, uint8_t* d, float* m);
-void rex_launch_step_body(RexSim* s, int blocks, hipStream_t st, const float* a, float* o, float* r, uint8_t* d, float* m);
-void rex_launch_step_base_trace(RexSim* s, int blocks, hipStream_t st, const float* a, float* o, float* r, uint8_t* d, float* m);
-void rex_launch_step_arm_trace(RexSim* s, int blocks, hipStream_t st, const float* a, float* o, float* r, uint8_t* d, float* m);
-void rex_launch_step_mixed_base_trace(RexSim* s, int blocks, hipStream_t st, const float* a, float* o, float* r, uint8_t* d, float* m);
-void rex_launch_step_mixed_arm_trace(RexSim* s, int blocks, hipStream_t st, const float* a, float* o, float* r, uint8_t* d, float* m);
-void rex_launch_step_body_trace(RexSim* s, int blocks, hipStream_t st, const float* a, float* o, float* r, uint8_t* d, float* m);
-void rex_launch_step_base_seg(RexSim* s, int blocks, hipStream_t st, const float* a, float* o, float* r, uint8_t* d, float* m);
-void rex_launch_step_arm_seg(RexSim* s, int blocks, hipStream_t st, const float* a, float* o, float* r, uint8_t* d, float* m);
-void rex_launch_step_mixed_base_seg(RexSim* s, int blocks, hipStream_t st, const float* a, float* o, float* r, uint8_t* d, float* m);
-void rex_launch_step_mixed_arm_seg(RexSim* s, int blocks, hipStream_t st, const float* a, float* o, float* r, uint8_t* d, float* m);
-void rex_launch_step_body_seg(RexSim* s, int blocks, hipStream_t st, const float* a, float* o, float* r, uint8_t* d, float* m);
-void rex_launch_step_base_pol(RexSim* s, int blocks, hipStream_t st, const float* a, float* o, float* r, uint8_t* d, float* m);
-void rex_launch_step_arm_pol(RexSim* s, int blocks, hipStream_t st, const float* a, float* o, float* r, uint8_t* d, float* m);
-void rex_launch_step_base_rnn(RexSim* s, int blocks, hipStream_t st, const float* a, float* o, float* r, uint8_t* d, float* m);
-void rex_launch_step_arm_rnn(RexSim* s, int blocks, hipStream_t st, const float* a, float* o, float* r, uint8_t* d, float* m);
-void rex_launch_step_base_mseg(RexSim* s, int blocks, hipStream_t st, const float* a, float* o, float* r, uint8_t* d, float* m);
-void rex_launch_step_arm_mseg(RexSim* s, int blocks, hipStream_t st, const float* a, float* o, float* r, uint8_t* d, float* m);
-void rex_launch_step_mixed_base_mseg(RexSim* s, int blocks, hipStream_t st, const float* a, float* o, float* r, uint8_t* d, float* m);
-void rex_launch_step_mixed_arm_mseg(RexSim* s, int blocks, hipStream_t st, const float* a, float* o, float* r, uint8_t* d, float* m);
-void rex_launch_step_body_mseg(RexSim* s, int blocks, hipStream_t st, const float* a, float* o, float* r, uint8_t* d, float* m);
-void rex_launch_step_base_mpol(RexSim* s, int blocks, hipStream_t st, const float* a, float* o, float* r, uint8_t* d, float* m);
-void rex_launch_step_arm_mpol(RexSim* s, int blocks, hipStream_t st, const float* a, float* o, float* r, uint8_t* d, float* m);
-void rex_launch_step_base_mrnn(RexSim* s, int blocks, hipStream_t st, const float* a, float* o, float* r, uint8_t* d, float* m);
-void rex_launch_step_arm_mrnn(RexSim* s, int blocks, hipStream_t st, const float* a, float* o, float* r, uint8_t* d, float* m);
-void rex_launch_settle_base(RexSim* s, int nrec, hipStream_t st, float* snap);   // <false, *>
-void rex_launch_settle_arm(RexSim* s, int nrec, hipStream_t st, float* snap);    // <true, *>
-
-// Every step translation unit is compiled twice (rex_gym_amd/build.py): as it is -- the product kernels -- and with
-// -DREX_TU_TRACE=1, the instantiations with the event trace compiled in (rex_set_event_trace; launcher names end in _trace)
-#ifndef REX_TU_TRACE
-#define REX_TU_TRACE 0
-#endif
-#ifndef REX_TU_SEG
-#define REX_TU_SEG 0      /* -DREX_TU_SEG=1: the segment instantiations (rex_step_segment; launcher names end in _seg) */
-#endif
-#ifndef REX_TU_POL
-#define REX_TU_POL 0      /* -DREX_TU_POL=1: the fused-actor instantiations (rex_step_policy / rex_step_segment_policy; launcher names end in _pol) */
-#endif
-#ifndef REX_TU_RNN
-#define REX_TU_RNN 0      /* -DREX_TU_RNN=1: the recurrent fused-actor instantiations (rex_set_policy_recurrent; launcher names end in _rnn) */
+// ---- the variants of the step kernel: one key (group, mode, MOTOR), one launcher template, one predicate ----
+// group: which rex_step_*.hip instantiates the kernels (the robot's mark, REX_TASK_MIXED, link-box contact rows)
+enum RexStepGroup { REX_GROUP_BASE, REX_GROUP_ARM, REX_GROUP_MIXED_BASE, REX_GROUP_MIXED_ARM, REX_GROUP_BODY, REX_NUM_GROUPS };
+// mode: every step unit is compiled once per mode it offers (rex_gym_amd/build.py variant_jobs: -DREX_TU_MODE=<mode>)
+//   STEP   the product kernels of rex_step (no define: a bare hipcc -c of a unit compiles these)
+//   TRACE  the instantiations with the event trace compiled in (rex_set_event_trace, a debug aid of the parity tests): the product
+//          kernels carry none of it
+//   SEG    the instantiations behind rex_step_segment (a loop over the steps of a rollout segment around the step), kept apart because
+//          the loop costs registers -- what the body forms from loop invariants is hoisted -- and rex_step's own kernels stay exactly
+//          what they were
+//   POL    the segment kernels with the reference's Gaussian MLP actor evaluated in front of every step (rex_step_policy /
+//          rex_step_segment_policy, rex_policy.h)
+//   RNN    the same with the reference's RECURRENT actor (a GRU cell on a per-env state, rex_set_policy_recurrent), kept apart so that
+//          the forward actor's kernels stay exactly what they were
+// -DREX_TU_MOT=1 next to SEG, POL or RNN: the same kernels reading the per-env actuator parameters (MOTOR; rex_set_motor_params /
+// rex_set_motor_randomization; rex_step runs them as a segment of one step), kept apart because the parameter loads and draws cost
+// registers: every other kernel stays exactly what it was
+enum RexStepMode { REX_MODE_STEP, REX_MODE_TRACE, REX_MODE_SEG, REX_MODE_POL, REX_MODE_RNN, REX_NUM_MODES };
+#ifndef REX_TU_MODE
+#define REX_TU_MODE REX_MODE_STEP
 #endif
 #ifndef REX_TU_MOT
-#define REX_TU_MOT 0      /* -DREX_TU_MOT=1 next to _SEG, _POL or _RNN: the same instantiations with the per-env actuator parameters (MOTOR; launcher names _mseg, _mpol, _mrnn) */
+#define REX_TU_MOT 0
 #endif
-#if REX_TU_MOT && REX_TU_SEG
-#define REX_STEP_LAUNCHER(group) rex_launch_step_##group##_mseg
-#elif REX_TU_MOT && REX_TU_POL
-#define REX_STEP_LAUNCHER(group) rex_launch_step_##group##_mpol
-#elif REX_TU_MOT && REX_TU_RNN
-#define REX_STEP_LAUNCHER(group) rex_launch_step_##group##_mrnn
-#elif REX_TU_TRACE
-#define REX_STEP_LAUNCHER(group) rex_launch_step_##group##_trace
-#elif REX_TU_SEG
-#define REX_STEP_LAUNCHER(group) rex_launch_step_##group##_seg
-#elif REX_TU_POL
-#define REX_STEP_LAUNCHER(group) rex_launch_step_##group##_pol
-#elif REX_TU_RNN
-#define REX_STEP_LAUNCHER(group) rex_launch_step_##group##_rnn
-#else
-#define REX_STEP_LAUNCHER(group) rex_launch_step_##group
-#endif
+constexpr bool rex_mode_has_actor(int mode) { return mode == REX_MODE_POL || mode == REX_MODE_RNN; }
+// which (group, mode, MOTOR) exist: the fused actor runs in the single-task toes-only kernels, the actuator parameters in the
+// segment-shaped ones.  build.py's variant_offered() is the same rule for the build matrix.
+constexpr bool rex_step_variant_offered(int group, int mode, bool motor) {
+  return (!rex_mode_has_actor(mode) || group == REX_GROUP_BASE || group == REX_GROUP_ARM) && (!motor || mode == REX_MODE_SEG || rex_mode_has_actor(mode));
+}
+// launchers: every offered key is one explicit specialisation, each in its own translation unit (rexsim.hip keeps their table)
+template <int GROUP, int MODE, bool MOTOR>
+void rex_launch_step(RexSim* s, int blocks, hipStream_t st, const float* a, float* o, float* r, uint8_t* d, float* m);
+template <bool ARM>
+void rex_launch_settle(RexSim* s, int nrec, hipStream_t st, float* snap);
+
 // the last argument of a step launch: the actor's part (P = NoPol / PolDev / RnnDev), for the MOTOR instantiations with the actuator's knobs behind it
 template <bool MOTOR, class P>
 static typename std::conditional<MOTOR, rex::WithMot<P>, P>::type rex_step_arg(const RexSim* s, const P& pol) {
   if constexpr (MOTOR) { rex::WithMot<P> w; static_cast<P&>(w) = pol; w.mot = s->mot; return w; }
   else return pol;
 }
-// the fused-actor kernels: four one-wave blocks to a workgroup; the actor's weights in dynamic LDS where they fit (RexSim::pol_lds_bytes, rex_set_policy)
-template <int EPW, bool ARM, bool MOTOR = false>
-static void rex_launch_policy_kernel(RexSim* s, int blocks, hipStream_t st, const float* a, float* o, float* r, uint8_t* d, float* m) {
-  auto kern = rex::rex_step_kernel<EPW, ARM, false, false, false, true, true, false, MOTOR>;
-  int& attr_bytes = s->pol_attr_bytes[MOTOR ? 1 : 0];   // (a sim launches either instantiation, as parameters are set and removed: one record each)
-  if (s->pol_lds_bytes > attr_bytes) {      // (per sim, i.e. per device: the attribute belongs to the function on the current device)
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, s->pol_lds_bytes);
-    attr_bytes = s->pol_lds_bytes;
+template <int EPW, bool ARM, bool MIXED, bool BODY, int MODE, bool MOTOR>
+static void rex_launch_step_kernel(RexSim* s, int blocks, hipStream_t st, const float* a, float* o, float* r, uint8_t* d, float* m) {
+  auto kern = rex::rex_step_kernel<EPW, ARM, MIXED, BODY, MODE == REX_MODE_TRACE, MODE == REX_MODE_SEG || rex_mode_has_actor(MODE), rex_mode_has_actor(MODE),
+                                   MODE == REX_MODE_RNN, MOTOR>;
+  if constexpr (MODE == REX_MODE_POL) {
+    // the fused-actor kernels: four one-wave blocks to a workgroup; the actor's weights in dynamic LDS where they fit (RexSim::pol_lds_bytes, rex_set_policy)
+    int& attr_bytes = s->pol_attr_bytes[MOTOR ? 1 : 0];   // (a sim launches either instantiation, as parameters are set and removed: one record each)
+    if (s->pol_lds_bytes > attr_bytes) {      // (per sim, i.e. per device: the attribute belongs to the function on the current device)
+      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, s->pol_lds_bytes);
+      attr_bytes = s->pol_lds_bytes;
+    }
+    constexpr int W = REX_POLICY_WAVES(EPW);
+    hipLaunchKernelGGL(kern, dim3((blocks + W - 1) / W), dim3(REX_WAVE * W), (size_t)s->pol_lds_bytes, st,
+                       s->dev, s->d_state, s->d_snap, a, o, r, d, m, rex_step_arg<MOTOR>(s, s->pol));
+  } else if constexpr (MODE == REX_MODE_RNN) {
+    // the recurrent fused-actor kernels: one-wave workgroups, no dynamic LDS (the weights are streamed)
+    rex::RnnDev pol;
+    static_cast<rex::PolDev&>(pol) = s->pol;
+    pol.state = s->d_rnn_state;
+    hipLaunchKernelGGL(kern, dim3(blocks), dim3(REX_WAVE), 0, st, s->dev, s->d_state, s->d_snap, a, o, r, d, m, rex_step_arg<MOTOR>(s, pol));
+  } else {
+    hipLaunchKernelGGL(kern, dim3(blocks), dim3(REX_WAVE), 0, st, s->dev, s->d_state, s->d_snap, a, o, r, d, m, rex_step_arg<MOTOR>(s, rex::NoPol{}));
   }
-  constexpr int W = REX_POLICY_WAVES(EPW);
-  hipLaunchKernelGGL(kern, dim3((blocks + W - 1) / W), dim3(REX_WAVE * W), (size_t)s->pol_lds_bytes, st,
-                     s->dev, s->d_state, s->d_snap, a, o, r, d, m, rex_step_arg<MOTOR>(s, s->pol));
 }
-// the recurrent fused-actor kernels: one-wave workgroups, no dynamic LDS (the weights are streamed)
-template <int EPW, bool ARM, bool MOTOR = false>
-static void rex_launch_rnn_kernel(RexSim* s, int blocks, hipStream_t st, const float* a, float* o, float* r, uint8_t* d, float* m) {
-  rex::RnnDev pol;
-  static_cast<rex::PolDev&>(pol) = s->pol;
-  pol.state = s->d_rnn_state;
-  hipLaunchKernelGGL((rex::rex_step_kernel<EPW, ARM, false, false, false, true, true, true, MOTOR>), dim3(blocks), dim3(REX_WAVE), 0, st,
-                     s->dev, s->d_state, s->d_snap, a, o, r, d, m, rex_step_arg<MOTOR>(s, pol));
-}
-#if REX_TU_POL
-#define REX_LAUNCH_STEP(EPW, ARM, MIXED, BODY) rex_launch_policy_kernel<EPW, ARM, REX_TU_MOT != 0>(s, blocks, st, a, o, r, d, m)
-#elif REX_TU_RNN
-#define REX_LAUNCH_STEP(EPW, ARM, MIXED, BODY) rex_launch_rnn_kernel<EPW, ARM, REX_TU_MOT != 0>(s, blocks, st, a, o, r, d, m)
-#else
-#define REX_LAUNCH_STEP(EPW, ARM, MIXED, BODY)                                                                                  \
-  hipLaunchKernelGGL((rex::rex_step_kernel<EPW, ARM, MIXED, BODY, REX_TU_TRACE != 0, REX_TU_SEG != 0, false, false, REX_TU_MOT != 0>), dim3(blocks), dim3(REX_WAVE), 0, st, s->dev, s->d_state, s->d_snap, \
-                     a, o, r, d, m, rex_step_arg<REX_TU_MOT != 0>(s, rex::NoPol{}))
-#endif
+// inside a unit's specialisation of rex_launch_step: the instantiations of its mode
+#define REX_LAUNCH_STEP(EPW, ARM, MIXED, BODY) rex_launch_step_kernel<EPW, ARM, MIXED, BODY, REX_TU_MODE, REX_TU_MOT != 0>(s, blocks, st, a, o, r, d, m)
 #define REX_LAUNCH_BY_EPW(ARM, MIXED, BODY)                                           \
   do {                                                                                \
     if (s->epw == 4) REX_LAUNCH_STEP(4, ARM, MIXED, BODY);                            \

@@ -15,6 +15,18 @@ namespace rex {
 
 // rex_set_policy: the caller's plain arrays (input-major weight matrices) -> the packed actor.  One thread per destination float.
 struct PolSrc { const float *w1, *b1, *w2, *b2, *w3, *b3, *logstd, *mean, *scale; };
+// the tail both packed actors end in, destination float t >= o_w3: the output layer [IN][A], its bias, logstd, the observ filter's mean
+// and scale [O] (0 / 1 without a filter); zero padding in between
+__device__ __forceinline__ float pack_tail(int t, int o_w3, int o_b3, int o_logstd, int o_mean, int o_scale, int IN, int O, int A, const float* w3, const float* b3,
+                                           const float* logstd, const float* mean, const float* scale) {
+  float v = 0.0f;
+  if (t < o_b3) { if (t - o_w3 < IN * A) v = w3[t - o_w3]; }
+  else if (t < o_logstd) { if (t - o_b3 < A) v = b3[t - o_b3]; }
+  else if (t < o_mean) { if (t - o_logstd < A) v = logstd[t - o_logstd]; }
+  else if (t < o_scale) { if (t - o_mean < O && mean) v = mean[t - o_mean]; }
+  else if (t < o_scale + O) { v = scale ? scale[t - o_scale] : 1.0f; }
+  return v;
+}
 __global__ void rex_pack_policy_kernel(PolSrc s, int O, int A, int H1, int H2, float* __restrict__ dst) {
   const PolOff o = policy_offsets(O, A, H1, H2);
   for (int t = blockIdx.x * blockDim.x + threadIdx.x; t < o.total; t += gridDim.x * blockDim.x) {
@@ -23,11 +35,7 @@ __global__ void rex_pack_policy_kernel(PolSrc s, int O, int A, int H1, int H2, f
     else if (t < o.w2) { if (t - o.b1 < H1) v = s.b1[t - o.b1]; }
     else if (t < o.b2) { const int u = t - o.w2, r = u & 3, j = (u >> 2) % H2, k = 4 * ((u >> 2) / H2) + r; if (k < H1) v = s.w2[k * H2 + j]; }
     else if (t < o.w3) { if (t - o.b2 < H2) v = s.b2[t - o.b2]; }
-    else if (t < o.b3) { if (t - o.w3 < H2 * A) v = s.w3[t - o.w3]; }
-    else if (t < o.logstd) { if (t - o.b3 < A) v = s.b3[t - o.b3]; }
-    else if (t < o.mean) { if (t - o.logstd < A) v = s.logstd[t - o.logstd]; }
-    else if (t < o.scale) { if (t - o.mean < O && s.mean) v = s.mean[t - o.mean]; }
-    else if (t < o.scale + O) { v = s.scale ? s.scale[t - o.scale] : 1.0f; }
+    else v = pack_tail(t, o.w3, o.b3, o.logstd, o.mean, o.scale, H2, O, A, s.w3, s.b3, s.logstd, s.mean, s.scale);
     dst[t] = v;
   }
 }
@@ -54,11 +62,7 @@ __global__ void rex_pack_rnn_kernel(RnnSrc s, int O, int A, int H1, int S, float
     else if (t < o.wc) { if (t - o.bu < S) v = s.bg[S + t - o.bu]; }
     else if (t < o.bc) v = rnn_gate_weight(t - o.wc, H1, S, s.wc, S, 0);
     else if (t < o.w3) { if (t - o.bc < S) v = s.bc[t - o.bc]; }
-    else if (t < o.b3) { if (t - o.w3 < S * A) v = s.w3[t - o.w3]; }
-    else if (t < o.logstd) { if (t - o.b3 < A) v = s.b3[t - o.b3]; }
-    else if (t < o.mean) { if (t - o.logstd < A) v = s.logstd[t - o.logstd]; }
-    else if (t < o.scale) { if (t - o.mean < O && s.mean) v = s.mean[t - o.mean]; }
-    else if (t < o.scale + O) { v = s.scale ? s.scale[t - o.scale] : 1.0f; }
+    else v = pack_tail(t, o.w3, o.b3, o.logstd, o.mean, o.scale, S, O, A, s.w3, s.b3, s.logstd, s.mean, s.scale);
     dst[t] = v;
   }
 }
@@ -362,8 +366,14 @@ static int pick_envs_per_wave(int n) {
 }
 
 // kernel instantiations by (envs per wave, mark); the arm rows fit 4 or 16 envs per workgroup in LDS
-static void launch_step(RexSim* s, int blocks, hipStream_t st, const float* a, float* o, float* r, uint8_t* d, float* m);
-static void launch_settle(RexSim* s, int nrec, hipStream_t st, float* snap);
+static int launch_step(RexSim* s, int blocks, hipStream_t st, const float* a, float* o, float* r, uint8_t* d, float* m);
+static int launch_settle(RexSim* s, int nrec, hipStream_t st, float* snap);
+static int step_group(const RexSim* s) {   // the variant group (rex_kernels.h RexStepGroup) whose kernels step this sim
+  const bool arm = s->cfg.mark == REX_MARK_ARM;
+  if (s->cfg.task == REX_TASK_MIXED) return arm ? REX_GROUP_MIXED_ARM : REX_GROUP_MIXED_BASE;   // lane groups only (rex_create caps the envs per wave at 16)
+  if (s->cfg.body_contacts) return REX_GROUP_BODY;                                              // link-box contact rows: 4 or 8 envs per wave (rex_create caps it)
+  return arm ? REX_GROUP_ARM : REX_GROUP_BASE;
+}
 
 // RexConfig carries its settings as float32; the reference computes its substep counts from the Python floats the
 // caller wrote (int(0.5 / 0.001) = 500, int(0.02 / 0.001) = 20), whose float32 quotients fall just below the integer.
@@ -626,7 +636,8 @@ int rex_create(const RexConfig* cfg, int device, float* d_state, void* stream, R
   for (int k = 0; k < REX_TIMING_RING; ++k) { s->ring0[k] = nullptr; s->ring1[k] = nullptr; }
   s->timed_steps = 0;
   hipStream_t st = (hipStream_t)stream;
-  launch_settle(s, d.n_mix, st, s->d_snap);
+  rc = launch_settle(s, d.n_mix, st, s->d_snap);
+  if (rc != REX_OK) { (void)rex_destroy(s); return rc; }
   e = hipGetLastError();
   if (e == hipSuccess) e = hipMemsetAsync(d_state, 0, sizeof(float) * (size_t)s->words * cfg->num_envs, st);
   if (e == hipSuccess) e = hipStreamSynchronize(st);
@@ -650,7 +661,8 @@ static int install_terrain(RexSim* s, const float* d_heights, const float* d_mid
   s->dev.terrain = k > 0 ? d_heights : nullptr;
   s->dev.terrain_mid = k > 0 ? d_mids : nullptr;
   s->dev.n_terrain = k;
-  launch_settle(s, nrec, st, s->d_snap);
+  const int rc = launch_settle(s, nrec, st, s->d_snap);
+  if (rc != REX_OK) return rc;
   HIPCHK(hipGetLastError());
   HIPCHK(hipStreamSynchronize(st));
   return REX_OK;
@@ -809,29 +821,53 @@ static int rows_floats_per_env(const RexSim* s) {   // the contact-row region of
   return 4 * (arm ? REX_LDS_F4_PER_ENV_ARM_OF(s->epw) : REX_ROWS_F4_OF(legf4));
 }
 
+// what rex_set_policy and rex_set_policy_recurrent share: may this sim run a fused actor at all, the checks in the order the caller has
+// always met them (the entry point's own -- its layer sizes against the LDS scratch, its null pointers -- sit between the dimensions and
+// obs_clip), the packed actor's buffer grown to `total` floats and the fields of PolDev that do not depend on the kind of actor
+extern "C++" {   // (a template, inside the ABI's extern "C")
+template <class OwnChecks>
+static int policy_install_common(RexSim* s, const char* who, int obs_dim, int action_dim, const float* d_obs_mean, float obs_clip, int sample, uint64_t seed,
+                                 OwnChecks own_checks) {
+  if (!rex_step_variant_offered(step_group(s), REX_MODE_POL, false) || s->epw > 16)   // (POL and RNN are offered to the same groups)
+    return fail(REX_EINVAL, "%s: the fused actor runs in the single-task lane-group kernels (not REX_TASK_MIXED, body_contacts = 0, REX_ENVS_PER_WAVE <= 16)", who);
+  if (!s->cfg.range_normalize)
+    return fail(REX_EINVAL, "%s: the sim must fold the reference's wrapper stack (RexConfig.range_normalize = 1): the agents act through "
+                            "RangeNormalize + ClipAction (playground/trainer.py:48-52)", who);
+  if (obs_dim != rex_obs_dim(&s->cfg) || action_dim != rex_action_dim(&s->cfg))
+    return failf(REX_EINVAL, "%s: obs_dim / action_dim %d / %d do not match the sim's %d / %d", who, obs_dim, action_dim, rex_obs_dim(&s->cfg), rex_action_dim(&s->cfg));
+  int total = 0;      // floats of the packed actor: the entry point's checks work it out from the sizes they have accepted
+  const int rc = own_checks(&total);
+  if (rc != REX_OK) return rc;
+  if (!(obs_clip > 0.0f) && d_obs_mean) return fail(REX_EINVAL, "%s: obs_clip must be positive", who);
+  HIPCHK(hipSetDevice(s->device));
+  if (total > s->polbuf_floats) {            // (one buffer, one policy installed at a time; a launch may still be reading the old buffer: the free below waits for the device)
+    if (s->d_polbuf) { HIPCHK(hipDeviceSynchronize()); (void)hipFree(s->d_polbuf); s->d_polbuf = nullptr; s->polbuf_floats = 0; }
+    if (hipMalloc(&s->d_polbuf, sizeof(float) * (size_t)total) != hipSuccess) return fail(REX_ENOMEM, "%s: hipMalloc", who);
+    s->polbuf_floats = total;
+  }
+  rex::PolDev& d = s->pol;
+  d.pk = s->d_polbuf; d.obs_in = nullptr; d.action_out = nullptr; d.mean_out = nullptr;
+  d.obs_clip = d_obs_mean ? obs_clip : 0.0f; d.sample = sample ? 1 : 0;
+  d.seed_lo = (uint32_t)seed; d.seed_hi = (uint32_t)(seed >> 32);
+  return REX_OK;
+}
+}
+
 int rex_set_policy(RexSim* s, const RexPolicy* p, void* stream) {
   if (!s) return fail(REX_EINVAL, "rex_set_policy: null sim%s", "");
   if (!p) { s->have_policy = 0; return REX_OK; }
-  if (s->cfg.task == REX_TASK_MIXED || s->cfg.body_contacts || s->epw > 16)
-    return fail(REX_EINVAL, "rex_set_policy: the fused actor runs in the single-task lane-group kernels (not REX_TASK_MIXED, body_contacts = 0, REX_ENVS_PER_WAVE <= 16)%s", "");
-  if (!s->cfg.range_normalize)
-    return fail(REX_EINVAL, "rex_set_policy: the sim must fold the reference's wrapper stack (RexConfig.range_normalize = 1): the agents act through "
-                            "RangeNormalize + ClipAction (playground/trainer.py:48-52)%s", "");
-  if (p->obs_dim != rex_obs_dim(&s->cfg) || p->action_dim != rex_action_dim(&s->cfg))
-    return failf(REX_EINVAL, "rex_set_policy: obs_dim / action_dim %d / %d do not match the sim's %d / %d", p->obs_dim, p->action_dim, rex_obs_dim(&s->cfg), rex_action_dim(&s->cfg));
-  if (p->hidden1 < 1 || p->hidden2 < 1 || p->hidden1 > 4096 || p->hidden2 > 4096 || rex::policy_scratch_floats(p->obs_dim, p->hidden1, p->hidden2) > rows_floats_per_env(s))
-    return failf(REX_EINVAL, "rex_set_policy: hidden layers of %d and %d units need %d floats of LDS per env, this kernel variant has %d", p->hidden1, p->hidden2,
-                 rex::policy_scratch_floats(p->obs_dim, p->hidden1 > 0 ? p->hidden1 : 0, p->hidden2 > 0 ? p->hidden2 : 0), rows_floats_per_env(s));
-  if (!p->d_w1 || !p->d_b1 || !p->d_w2 || !p->d_b2 || !p->d_w3 || !p->d_b3 || !p->d_logstd || (!p->d_obs_mean) != (!p->d_obs_scale))
-    return fail(REX_EINVAL, "rex_set_policy: null weight pointer (d_obs_mean and d_obs_scale go together)%s", "");
-  if (!(p->obs_clip > 0.0f) && p->d_obs_mean) return fail(REX_EINVAL, "rex_set_policy: obs_clip must be positive%s", "");
-  HIPCHK(hipSetDevice(s->device));
-  const rex::PolOff off = rex::policy_offsets(p->obs_dim, p->action_dim, p->hidden1, p->hidden2);
-  if (off.total > s->polbuf_floats) {            // (a launch that is still reading the old buffer: the free below waits for the device)
-    if (s->d_polbuf) { HIPCHK(hipDeviceSynchronize()); (void)hipFree(s->d_polbuf); s->d_polbuf = nullptr; s->polbuf_floats = 0; }
-    if (hipMalloc(&s->d_polbuf, sizeof(float) * (size_t)off.total) != hipSuccess) return fail(REX_ENOMEM, "rex_set_policy: hipMalloc%s", "");
-    s->polbuf_floats = off.total;
-  }
+  rex::PolOff off;
+  const int rc = policy_install_common(s, "rex_set_policy", p->obs_dim, p->action_dim, p->d_obs_mean, p->obs_clip, p->sample, p->seed, [&](int* total) {
+    if (p->hidden1 < 1 || p->hidden2 < 1 || p->hidden1 > 4096 || p->hidden2 > 4096 || rex::policy_scratch_floats(p->obs_dim, p->hidden1, p->hidden2) > rows_floats_per_env(s))
+      return failf(REX_EINVAL, "rex_set_policy: hidden layers of %d and %d units need %d floats of LDS per env, this kernel variant has %d", p->hidden1, p->hidden2,
+                   rex::policy_scratch_floats(p->obs_dim, p->hidden1 > 0 ? p->hidden1 : 0, p->hidden2 > 0 ? p->hidden2 : 0), rows_floats_per_env(s));
+    if (!p->d_w1 || !p->d_b1 || !p->d_w2 || !p->d_b2 || !p->d_w3 || !p->d_b3 || !p->d_logstd || (!p->d_obs_mean) != (!p->d_obs_scale))
+      return fail(REX_EINVAL, "rex_set_policy: null weight pointer (d_obs_mean and d_obs_scale go together)%s", "");
+    off = rex::policy_offsets(p->obs_dim, p->action_dim, p->hidden1, p->hidden2);
+    *total = off.total;
+    return (int)REX_OK;
+  });
+  if (rc != REX_OK) return rc;
   // pack (stream-ordered: behind the launches that read the previous contents, ahead of those that follow): input-major matrices ->
   // [k / 4][unit][4], every block 16-byte aligned, zero padding (rex_policy.h)
   rex::PolSrc src{p->d_w1, p->d_b1, p->d_w2, p->d_b2, p->d_w3, p->d_b3, p->d_logstd, p->d_obs_mean, p->d_obs_scale};
@@ -839,9 +875,7 @@ int rex_set_policy(RexSim* s, const RexPolicy* p, void* stream) {
                      p->hidden2, s->d_polbuf);
   HIPCHK(hipGetLastError());
   rex::PolDev& d = s->pol;
-  d.pk = s->d_polbuf; d.obs_in = nullptr; d.action_out = nullptr; d.mean_out = nullptr;
-  d.h1 = p->hidden1; d.h2 = p->hidden2; d.obs_clip = p->d_obs_mean ? p->obs_clip : 0.0f; d.sample = p->sample ? 1 : 0;
-  d.seed_lo = (uint32_t)p->seed; d.seed_hi = (uint32_t)(p->seed >> 32);
+  d.h1 = p->hidden1; d.h2 = p->hidden2;
   {   // one copy of the packed actor per four-wave workgroup, in dynamic LDS, if it fits next to the waves' rows (MI355X: 160 KB per CU)
     const bool arm = s->cfg.mark == REX_MARK_ARM;
     const int wave_bytes = (rows_floats_per_env(s) / 4 + REX_PARK_F4_OF(s->epw, arm)) * s->epw * 16;
@@ -858,37 +892,27 @@ int rex_set_policy(RexSim* s, const RexPolicy* p, void* stream) {
 int rex_set_policy_recurrent(RexSim* s, const RexRecurrentPolicy* p, void* stream) {
   if (!s) return fail(REX_EINVAL, "rex_set_policy_recurrent: null sim%s", "");
   if (!p) { s->have_policy = 0; return REX_OK; }
-  if (s->cfg.task == REX_TASK_MIXED || s->cfg.body_contacts || s->epw > 16)
-    return fail(REX_EINVAL, "rex_set_policy_recurrent: the fused actor runs in the single-task lane-group kernels (not REX_TASK_MIXED, body_contacts = 0, REX_ENVS_PER_WAVE <= 16)%s", "");
-  if (!s->cfg.range_normalize)
-    return fail(REX_EINVAL, "rex_set_policy_recurrent: the sim must fold the reference's wrapper stack (RexConfig.range_normalize = 1): the agents act through "
-                            "RangeNormalize + ClipAction (playground/trainer.py:48-52)%s", "");
-  if (p->obs_dim != rex_obs_dim(&s->cfg) || p->action_dim != rex_action_dim(&s->cfg))
-    return failf(REX_EINVAL, "rex_set_policy_recurrent: obs_dim / action_dim %d / %d do not match the sim's %d / %d", p->obs_dim, p->action_dim, rex_obs_dim(&s->cfg), rex_action_dim(&s->cfg));
-  if (p->state_size < 1 || p->state_size > REX_RNN_MAX_STATE)
-    return failf(REX_EINVAL, "rex_set_policy_recurrent: state_size %d: the cell is one matrix-core pass per gate, 1..%d units", p->state_size, REX_RNN_MAX_STATE);
-  if (p->hidden1 < 1 || p->hidden1 > 4096 || rex::rnn_scratch_floats(p->obs_dim, p->hidden1, p->state_size) > rows_floats_per_env(s))
-    return failf(REX_EINVAL, "rex_set_policy_recurrent: a layer of %d units and a cell of %d need %d floats of LDS per env, this kernel variant has %d", p->hidden1, p->state_size,
-                 rex::rnn_scratch_floats(p->obs_dim, p->hidden1 > 0 ? p->hidden1 : 0, p->state_size), rows_floats_per_env(s));
-  if (!p->d_w1 || !p->d_b1 || !p->d_wg || !p->d_bg || !p->d_wc || !p->d_bc || !p->d_w3 || !p->d_b3 || !p->d_logstd || (!p->d_obs_mean) != (!p->d_obs_scale))
-    return fail(REX_EINVAL, "rex_set_policy_recurrent: null weight pointer (d_obs_mean and d_obs_scale go together)%s", "");
-  if (!p->d_state) return fail(REX_EINVAL, "rex_set_policy_recurrent: null d_state (the GRU state [state_size][num_envs] is caller-owned)%s", "");
-  if (!(p->obs_clip > 0.0f) && p->d_obs_mean) return fail(REX_EINVAL, "rex_set_policy_recurrent: obs_clip must be positive%s", "");
-  HIPCHK(hipSetDevice(s->device));
-  const rex::RnnOff off = rex::rnn_offsets(p->obs_dim, p->action_dim, p->hidden1, p->state_size);
-  if (off.total > s->polbuf_floats) {            // (the buffer is shared with rex_set_policy: one policy is installed at a time)
-    if (s->d_polbuf) { HIPCHK(hipDeviceSynchronize()); (void)hipFree(s->d_polbuf); s->d_polbuf = nullptr; s->polbuf_floats = 0; }
-    if (hipMalloc(&s->d_polbuf, sizeof(float) * (size_t)off.total) != hipSuccess) return fail(REX_ENOMEM, "rex_set_policy_recurrent: hipMalloc%s", "");
-    s->polbuf_floats = off.total;
-  }
+  rex::RnnOff off;
+  const int rc = policy_install_common(s, "rex_set_policy_recurrent", p->obs_dim, p->action_dim, p->d_obs_mean, p->obs_clip, p->sample, p->seed, [&](int* total) {
+    if (p->state_size < 1 || p->state_size > REX_RNN_MAX_STATE)
+      return failf(REX_EINVAL, "rex_set_policy_recurrent: state_size %d: the cell is one matrix-core pass per gate, 1..%d units", p->state_size, REX_RNN_MAX_STATE);
+    if (p->hidden1 < 1 || p->hidden1 > 4096 || rex::rnn_scratch_floats(p->obs_dim, p->hidden1, p->state_size) > rows_floats_per_env(s))
+      return failf(REX_EINVAL, "rex_set_policy_recurrent: a layer of %d units and a cell of %d need %d floats of LDS per env, this kernel variant has %d", p->hidden1, p->state_size,
+                   rex::rnn_scratch_floats(p->obs_dim, p->hidden1 > 0 ? p->hidden1 : 0, p->state_size), rows_floats_per_env(s));
+    if (!p->d_w1 || !p->d_b1 || !p->d_wg || !p->d_bg || !p->d_wc || !p->d_bc || !p->d_w3 || !p->d_b3 || !p->d_logstd || (!p->d_obs_mean) != (!p->d_obs_scale))
+      return fail(REX_EINVAL, "rex_set_policy_recurrent: null weight pointer (d_obs_mean and d_obs_scale go together)%s", "");
+    if (!p->d_state) return fail(REX_EINVAL, "rex_set_policy_recurrent: null d_state (the GRU state [state_size][num_envs] is caller-owned)%s", "");
+    off = rex::rnn_offsets(p->obs_dim, p->action_dim, p->hidden1, p->state_size);
+    *total = off.total;
+    return (int)REX_OK;
+  });
+  if (rc != REX_OK) return rc;
   rex::RnnSrc src{p->d_w1, p->d_b1, p->d_wg, p->d_bg, p->d_wc, p->d_bc, p->d_w3, p->d_b3, p->d_logstd, p->d_obs_mean, p->d_obs_scale};
   hipLaunchKernelGGL(rex::rex_pack_rnn_kernel, dim3((off.total + 255) / 256), dim3(256), 0, (hipStream_t)stream, src, p->obs_dim, p->action_dim, p->hidden1,
                      p->state_size, s->d_polbuf);
   HIPCHK(hipGetLastError());
   rex::PolDev& d = s->pol;
-  d.pk = s->d_polbuf; d.obs_in = nullptr; d.action_out = nullptr; d.mean_out = nullptr;
-  d.h1 = p->hidden1; d.h2 = p->state_size; d.obs_clip = p->d_obs_mean ? p->obs_clip : 0.0f; d.sample = p->sample ? 1 : 0;
-  d.seed_lo = (uint32_t)p->seed; d.seed_hi = (uint32_t)(p->seed >> 32);
+  d.h1 = p->hidden1; d.h2 = p->state_size;
   d.in_lds = 0;                                  // 364 KB for 4-200-(100)-2: streamed from L2 at every envs-per-wave
   s->pol_lds_bytes = 0;
   s->d_rnn_state = p->d_state; s->rnn_state_size = p->state_size;
@@ -937,10 +961,11 @@ static int step_launch(RexSim* s, int num_steps, const float* d_action, float* d
     s->timed_steps++;                                         // launch, the queue stays as full as in an untimed run)
   } else s->dev.clock = nullptr;
   if (s->timing == 1 || s->timing == 2) HIPCHK(hipEventRecord(e0, st));
-  launch_step(s, blocks, st, d_action, d_obs, d_reward, d_done, d_motor_cmd);
+  int rc = launch_step(s, blocks, st, d_action, d_obs, d_reward, d_done, d_motor_cmd);
+  if (rc != REX_OK) return rc;
   {   // developer probe (tools/launch_gap.py): REX_STEP_REPEAT=R issues the launch R times back to back from C
     static const int repeat = getenv("REX_STEP_REPEAT") ? atoi(getenv("REX_STEP_REPEAT")) : 1;
-    for (int k = 1; k < repeat; ++k) launch_step(s, blocks, st, d_action, d_obs, d_reward, d_done, d_motor_cmd);
+    for (int k = 1; k < repeat; ++k) (void)launch_step(s, blocks, st, d_action, d_obs, d_reward, d_done, d_motor_cmd);
   }
   HIPCHK(hipGetLastError());
   // (the timed span is the step kernel's: the regrouping launches below are not part of it)
@@ -1218,53 +1243,58 @@ REX_API int rex_debug_prof2(long long* out, int reset) {   /* the sections of th
 #endif
 }  // extern "C"
 
-static void launch_step(RexSim* s, int blocks, hipStream_t st, const float* a, float* o, float* r, uint8_t* d, float* m) {
-  const bool arm = s->cfg.mark == REX_MARK_ARM;
-  if (s->dev.trace && s->dev.nsteps > 1) {   // a segment under the event trace (debug runs): step by step through the _trace kernels
+// ---- the launchers of every offered variant (rex_kernels.h), nullptr where a combination is not offered or its group was left out of
+// a developer build (build.py REX_BUILD_ONLY: -DREX_LEFT_OUT_GROUPS=<bit mask over RexStepGroup>) ----
+#ifndef REX_LEFT_OUT_GROUPS
+#define REX_LEFT_OUT_GROUPS 0
+#endif
+typedef void (*StepLauncher)(RexSim*, int, hipStream_t, const float*, float*, float*, uint8_t*, float*);
+typedef void (*SettleLauncher)(RexSim*, int, hipStream_t, float*);
+template <int GROUP, int MODE, bool MOTOR> static constexpr StepLauncher step_launcher() {
+  if constexpr (rex_step_variant_offered(GROUP, MODE, MOTOR) && !((REX_LEFT_OUT_GROUPS >> GROUP) & 1)) return &rex_launch_step<GROUP, MODE, MOTOR>;
+  else return nullptr;
+}
+template <bool ARM> static constexpr SettleLauncher settle_launcher() {
+  if constexpr (!((REX_LEFT_OUT_GROUPS >> (ARM ? REX_GROUP_ARM : REX_GROUP_BASE)) & 1)) return &rex_launch_settle<ARM>;
+  else return nullptr;
+}
+#define REX_TABLE_MODE(G, M) { step_launcher<G, M, false>(), step_launcher<G, M, true>() }
+#define REX_TABLE_GROUP(G) { REX_TABLE_MODE(G, REX_MODE_STEP), REX_TABLE_MODE(G, REX_MODE_TRACE), REX_TABLE_MODE(G, REX_MODE_SEG), REX_TABLE_MODE(G, REX_MODE_POL), REX_TABLE_MODE(G, REX_MODE_RNN) }
+static const StepLauncher step_launchers[REX_NUM_GROUPS][REX_NUM_MODES][2] = {
+    REX_TABLE_GROUP(REX_GROUP_BASE), REX_TABLE_GROUP(REX_GROUP_ARM), REX_TABLE_GROUP(REX_GROUP_MIXED_BASE), REX_TABLE_GROUP(REX_GROUP_MIXED_ARM), REX_TABLE_GROUP(REX_GROUP_BODY)};
+static const SettleLauncher settle_launchers[2] = {settle_launcher<false>(), settle_launcher<true>()};
+static const char* const group_names[REX_NUM_GROUPS] = {"base", "arm", "mixed_base", "mixed_arm", "body"};
+static const char* const mode_names[REX_NUM_MODES] = {"step", "trace", "segment", "fused-actor", "recurrent fused-actor"};
+
+static int launch_step(RexSim* s, int blocks, hipStream_t st, const float* a, float* o, float* r, uint8_t* d, float* m) {
+  if (s->dev.trace && s->dev.nsteps > 1) {   // a segment under the event trace (debug runs): step by step through the trace kernels
     const int T = s->dev.nsteps, n = s->cfg.num_envs;
     const int ad = rex_action_dim(&s->cfg), od = rex_obs_dim(&s->cfg), nm = rex_num_motors(&s->cfg);
+    int rc = REX_OK;
     s->dev.nsteps = 1;
-    for (int t = 0; t < T; ++t)
-      launch_step(s, blocks, st, a + (size_t)t * n * ad, o + (size_t)t * n * od, r + (size_t)t * n, d + (size_t)t * n, m ? m + (size_t)t * n * nm : nullptr);
+    for (int t = 0; t < T && rc == REX_OK; ++t)
+      rc = launch_step(s, blocks, st, a + (size_t)t * n * ad, o + (size_t)t * n * od, r + (size_t)t * n, d + (size_t)t * n, m ? m + (size_t)t * n * nm : nullptr);
     s->dev.nsteps = T;
-    return;
+    return rc;
   }
-  if (s->dev.trace) {   // rex_set_event_trace: the instantiations with the event trace compiled in (debug runs)
-    if (s->cfg.task == REX_TASK_MIXED) { if (arm) rex_launch_step_mixed_arm_trace(s, blocks, st, a, o, r, d, m); else rex_launch_step_mixed_base_trace(s, blocks, st, a, o, r, d, m); }
-    else if (s->cfg.body_contacts) rex_launch_step_body_trace(s, blocks, st, a, o, r, d, m);
-    else if (arm) rex_launch_step_arm_trace(s, blocks, st, a, o, r, d, m);
-    else rex_launch_step_base_trace(s, blocks, st, a, o, r, d, m);
-    return;
-  }
-  if (rex::motor_params_on(s->mot)) {   // rex_set_motor_params / rex_set_motor_randomization: the segment instantiations that read the actuator's knobs
-    if (s->use_policy) {                // (rex_step is a segment of one step: the same arithmetic, bit for bit)
-      if (s->have_policy == 2) { if (arm) rex_launch_step_arm_mrnn(s, blocks, st, a, o, r, d, m); else rex_launch_step_base_mrnn(s, blocks, st, a, o, r, d, m); }
-      else if (arm) rex_launch_step_arm_mpol(s, blocks, st, a, o, r, d, m); else rex_launch_step_base_mpol(s, blocks, st, a, o, r, d, m);
-    }
-    else if (s->cfg.task == REX_TASK_MIXED) { if (arm) rex_launch_step_mixed_arm_mseg(s, blocks, st, a, o, r, d, m); else rex_launch_step_mixed_base_mseg(s, blocks, st, a, o, r, d, m); }
-    else if (s->cfg.body_contacts) rex_launch_step_body_mseg(s, blocks, st, a, o, r, d, m);
-    else if (arm) rex_launch_step_arm_mseg(s, blocks, st, a, o, r, d, m);
-    else rex_launch_step_base_mseg(s, blocks, st, a, o, r, d, m);
-    return;
-  }
-  if (s->use_policy) {       // rex_step_policy / rex_step_segment_policy: the segment kernels with the actor in front of every step
-    if (s->have_policy == 2) { if (arm) rex_launch_step_arm_rnn(s, blocks, st, a, o, r, d, m); else rex_launch_step_base_rnn(s, blocks, st, a, o, r, d, m); }
-    else if (arm) rex_launch_step_arm_pol(s, blocks, st, a, o, r, d, m); else rex_launch_step_base_pol(s, blocks, st, a, o, r, d, m);
-    return;
-  }
-  if (s->dev.nsteps > 1) {   // rex_step_segment: the instantiations with the loop over the segment's steps
-    if (s->cfg.task == REX_TASK_MIXED) { if (arm) rex_launch_step_mixed_arm_seg(s, blocks, st, a, o, r, d, m); else rex_launch_step_mixed_base_seg(s, blocks, st, a, o, r, d, m); }
-    else if (s->cfg.body_contacts) rex_launch_step_body_seg(s, blocks, st, a, o, r, d, m);
-    else if (arm) rex_launch_step_arm_seg(s, blocks, st, a, o, r, d, m);
-    else rex_launch_step_base_seg(s, blocks, st, a, o, r, d, m);
-    return;
-  }
-  if (s->cfg.task == REX_TASK_MIXED) {   // lane groups only (rex_create caps the envs per wave at 16)
-    if (arm) rex_launch_step_mixed_arm(s, blocks, st, a, o, r, d, m); else rex_launch_step_mixed_base(s, blocks, st, a, o, r, d, m);
-  } else if (s->cfg.body_contacts) rex_launch_step_body(s, blocks, st, a, o, r, d, m);   // link-box contact rows: 4 or 8 envs per wave (rex_create caps it)
-  else if (arm) rex_launch_step_arm(s, blocks, st, a, o, r, d, m);
-  else rex_launch_step_base(s, blocks, st, a, o, r, d, m);
+  // rex_set_motor_params / rex_set_motor_randomization: the segment-shaped instantiations that read the actuator's knobs (rex_step is a
+  // segment of one step: the same arithmetic, bit for bit)
+  const bool motor = rex::motor_params_on(s->mot);
+  const int mode = s->dev.trace    ? REX_MODE_TRACE                                         // rex_set_event_trace (debug runs)
+                   : s->use_policy ? (s->have_policy == 2 ? REX_MODE_RNN : REX_MODE_POL)    // rex_step_policy / rex_step_segment_policy
+                   : (s->dev.nsteps > 1 || motor) ? REX_MODE_SEG : REX_MODE_STEP;           // rex_step_segment / rex_step
+  const int group = step_group(s);
+  const StepLauncher launch = step_launchers[group][mode][motor ? 1 : 0];
+  if (!launch)
+    return failf(REX_EINVAL, "this library has no %s kernels%s of variant group %s (not offered, or left out of a developer build: REX_BUILD_ONLY)", mode_names[mode],
+                 motor ? " with motor parameters" : "", group_names[group]);
+  launch(s, blocks, st, a, o, r, d, m);
+  return REX_OK;
 }
-static void launch_settle(RexSim* s, int nrec, hipStream_t st, float* snap) {
-  if (s->cfg.mark == REX_MARK_ARM) rex_launch_settle_arm(s, nrec, st, snap); else rex_launch_settle_base(s, nrec, st, snap);
+static int launch_settle(RexSim* s, int nrec, hipStream_t st, float* snap) {
+  const bool arm = s->cfg.mark == REX_MARK_ARM;
+  if (!settle_launchers[arm])
+    return failf(REX_EINVAL, "this library has no settle kernels of variant group %s (left out of a developer build: REX_BUILD_ONLY)", group_names[arm ? REX_GROUP_ARM : REX_GROUP_BASE]);
+  settle_launchers[arm](s, nrec, st, snap);
+  return REX_OK;
 }

@@ -891,6 +891,21 @@ def test_mark_arm_window_with_quiet_arm_rows(torch, tmp_path):
     assert rec["p99_rad"] <= 1e-3 and rec["median_rad"] <= 1e-4, (rec["median_rad"], rec["p99_rad"])
 
 
+def test_left_out_variant_group_is_an_error_return(torch):
+    """The diagnostic twin is built with only="arm,mixed_arm" (rex_gym_amd/build.py build_diag): its launcher table has no entry for the
+    other variant groups.  In a fresh process on that library, creating a base-mark sim is the package's ordinary error -- a host-side
+    return before any kernel launch, its message naming the left-out group -- and a mark-arm sim in the same process still resets and
+    takes a step; the process ends normally.  tests/diag_left_out_group.py."""
+    import os, subprocess, sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    from rex_gym_amd import build as hb
+    assert os.path.exists(hb.DIAG_LIB_PATH), "build the diagnostic twin first: python -m rex_gym_amd.build --diag (__graft_entry__.build() does)"
+    out = subprocess.run([sys.executable, os.path.join(root, "tests", "diag_left_out_group.py")], capture_output=True, text=True, timeout=300,
+                         cwd=root, env=dict(os.environ, REX_LIB_PATH=hb.DIAG_LIB_PATH))
+    assert out.returncode == 0, (out.returncode, out.stderr[-3000:])
+    assert "variant group base" in out.stdout, out.stdout
+
+
 @pytest.mark.parametrize("case", ["walk_ik", "mixed_arm", "walk_ik_policy"])
 def test_hip_shards_on_two_ranks_reproduce_the_single_process_batch(torch, case, tmp_path):
     """"seeds = base_seed (+) global_env_index so results are invariant to G" -- on the HIP path, across REAL ranks: two

@@ -20,6 +20,8 @@ def L():
 
 
 def test_library_exports_every_declared_symbol(L):
+    """Loading the library is part of the check: rexsim.hip's dispatch table holds the address of every offered step / settle launcher
+    as data, so a translation unit missing from the link fails here, at load time, not at the first call of its variant."""
     hdr = open(os.path.join(ROOT, "include", "rexsim.h")).read()
     declared = set(re.findall(r"REX_API\s+[\w\s\*]+?\b(rex_\w+)\s*\(", hdr))
     assert len(declared) >= 14
@@ -28,6 +30,36 @@ def test_library_exports_every_declared_symbol(L):
     for name in declared:
         assert hasattr(lib, name)
     assert lib.rex_abi_version() == L.ABI_VERSION == 6
+
+
+def test_build_matrix_is_the_offered_variants():
+    """build.variant_jobs() is the one list the object build, the unity build and the flags stamp are driven by: every step unit once per
+    (mode, MOTOR) that csrc/rex_kernels.h rex_step_variant_offered offers -- the fused actors (POL, RNN) for base and arm only, the
+    actuator parameters (MOT) for SEG, POL and RNN only -- plus the two settle units, the renderers and the C ABI.  33 objects: 28 step
+    jobs + 2 settle + 3 others.  The expected set is spelled out so that a change of the rule is a visible diff."""
+    from rex_gym_amd import build
+    all5 = ["arm", "base", "body", "mixed_arm", "mixed_base"]
+    single = ["arm", "base"]
+    expected_step = {   # (REX_TU_MODE, REX_TU_MOT) -> groups
+        (None, False): all5, ("TRACE", False): all5, ("SEG", False): all5, ("POL", False): single, ("RNN", False): single,
+        ("SEG", True): all5, ("POL", True): single, ("RNN", True): single}
+    expected = set()
+    for (mode, mot), groups in expected_step.items():
+        defines = ([] if mode is None else ["-DREX_TU_MODE=REX_MODE_" + mode]) + (["-DREX_TU_MOT=1"] if mot else [])
+        expected |= {("rex_step_%s.hip" % g, tuple(sorted(defines))) for g in groups}
+    assert len(expected) == 5 + 5 + 5 + 2 + 2 + 5 + 2 + 2 == 28
+    expected |= {(s, ()) for s in ("rex_settle_arm.hip", "rex_settle_base.hip", "rex_render.hip", "rex_render_mesh.hip", "rexsim.hip")}
+    jobs = build.variant_jobs()
+    pairs = [(s, tuple(sorted(d))) for s, _, d in jobs]
+    assert len(jobs) == 33 and len(set(pairs)) == len(pairs)
+    assert set(pairs) == expected, set(pairs) ^ expected
+    objects = [s[:-4] + tag for s, tag, _ in jobs]
+    assert len(set(objects)) == len(objects)          # the tags keep the object files apart
+    assert {tag for _, tag, _ in jobs} == {"", "_trace", "_seg", "_pol", "_rnn", "_mseg", "_mpol", "_mrnn"}
+    step = [(s, d) for s, d in pairs if s.startswith("rex_step_")]
+    assert not [j for j in step if ("mixed" in j[0] or "body" in j[0]) and any("POL" in x or "RNN" in x for x in j[1])]
+    assert not [j for j in step if "-DREX_TU_MOT=1" in j[1] and (not any("REX_TU_MODE" in x for x in j[1]) or "-DREX_TU_MODE=REX_MODE_TRACE" in j[1])]
+    assert pairs[-1][0] == "rexsim.hip"               # a unity build includes the launcher table behind the specialisations it names
 
 
 def test_default_config_matches_reference_constants(L):

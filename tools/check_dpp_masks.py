@@ -18,8 +18,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "rex_gym_amd", "csrc")
 OUT = os.path.join(ROOT, "scratch", "isa")
 os.makedirs(OUT, exist_ok=True)
-# --pol: the fused-actor instantiations (-DREX_TU_POL=1) of the groups instead of the product kernels, into scratch/isa_pol
-# --rnn: the recurrent fused-actor instantiations (-DREX_TU_RNN=1), into scratch/isa_rnn
+# --pol: the fused-actor instantiations (-DREX_TU_MODE=REX_MODE_POL) of the groups instead of the product kernels, into scratch/isa_pol
+# --rnn: the recurrent fused-actor instantiations (-DREX_TU_MODE=REX_MODE_RNN), into scratch/isa_rnn
 POL = "--pol" in sys.argv
 RNN = "--rnn" in sys.argv
 groups = [a for a in sys.argv[1:] if a not in ("--pol", "--rnn")] or (["step_base", "step_arm"] if POL or RNN else
@@ -34,7 +34,7 @@ from rex_gym_amd.build import COMPILE_FLAGS      # the library's own compile fla
 
 
 def compile_group(g):
-    subprocess.run(["hipcc"] + COMPILE_FLAGS + (["-DREX_TU_RNN=1"] if RNN else ["-DREX_TU_POL=1"] if POL else []) + ["-save-temps", "-I", CSRC, "-c",
+    subprocess.run(["hipcc"] + COMPILE_FLAGS + (["-DREX_TU_MODE=REX_MODE_RNN"] if RNN else ["-DREX_TU_MODE=REX_MODE_POL"] if POL else []) + ["-save-temps", "-I", CSRC, "-c",
                     os.path.join(CSRC, f"rex_{g}.hip"), "-o", os.devnull], cwd=OUT, check=True, stderr=subprocess.DEVNULL)
     return g
 

@@ -1,7 +1,8 @@
 #!/bin/bash
 # resource usage (AGPRs, scratch) of every kernel of one variant group's translation unit, with extra compiler flags:
 #   tools/kres.sh step_arm '-DREX_TARGET_BY_DIVISION(EPW,ARM)=0' ...
-#   tools/kres.sh step_base -DREX_TU_POL=1      the fused-actor kernels; -DREX_TU_RNN=1: the recurrent fused-actor kernels (step_base, step_arm)
+#   tools/kres.sh step_base -DREX_TU_MODE=REX_MODE_POL      the fused-actor kernels; REX_MODE_RNN: the recurrent ones (step_base, step_arm);
+#                           REX_MODE_TRACE / REX_MODE_SEG: any step unit; -DREX_TU_MOT=1 next to SEG, POL, RNN (csrc/rex_kernels.h RexStepMode)
 cd "$(dirname "$0")/.."
 G=$1; shift
 FLAGS=$(python -c "from rex_gym_amd.build import COMPILE_FLAGS; print(' '.join(COMPILE_FLAGS))")   # the library's own compile flags
