@@ -492,6 +492,58 @@ REX_API int rex_render_set_visuals(RexSim* sim, const float* nodes, int num_node
 REX_API int rex_render_visual(RexSim* sim, const RexCamera* cam, const int32_t* d_env_ids, int n, int width, int height,
                               uint8_t* d_rgb, float* d_depth, int16_t* d_seg, void* stream);
 
+/* ---- the fused PPO learner (csrc/rex_learner.h): the losses of the reference's KL-penalty PPO (agents/ppo/algorithm.py:289-301,
+ * 376-434) and their parameter gradients for a ForwardGaussianPolicy network (networks.py:69-112: obs_dim -> hidden1 -> hidden2 ->
+ * out_dim, two ReLU layers), one pass over the episode memory per call.  Stateless: no RexSim, the library allocates nothing -- the
+ * caller owns every buffer, the workspace included.  All device arrays float32, row-major; the episode memory is R rows (episodes) of T
+ * padded steps with a length per row (int32, clamped to 0..T): a step t >= length[r] contributes exactly nothing and is never read.
+ * Supported: obs_dim 4, 16 or 22; out_dim (the action dimension) 1, 2, 4 or 8 for the policy net and 1 for the value net; hidden1 <= 256,
+ * hidden2 <= 128; R * T * 24 < 2^31 (24 = the widest observation row, padded).  Anything else: REX_EINVAL, message in rex_last_error.
+ * Every sum runs in a fixed order: two calls on the same inputs return the same bits. */
+typedef struct RexPpoNet {                /* the network, in TORCH layout: a Linear's weight is [out][in], no transposes */
+  int32_t obs_dim, out_dim, hidden1, hidden2;
+  const float *d_w1, *d_b1;               /* [hidden1][obs_dim], [hidden1] */
+  const float *d_w2, *d_b2;               /* [hidden2][hidden1], [hidden2] */
+  const float *d_w3, *d_b3;               /* [out_dim][hidden2], [out_dim]: policy: mean = tanh(W3 h2 + b3); value = W3 h2 + b3 */
+  const float *d_logstd;                  /* [out_dim] (policy; NULL for the value net) */
+} RexPpoNet;
+typedef struct RexPpoBatch {
+  int32_t rows, steps;                    /* R, T */
+  const float *d_observ;                  /* [R][T][obs_dim], already through the observ filter */
+  const float *d_action, *d_old_mean, *d_old_logstd;   /* [R][T][out_dim] (policy) */
+  const float *d_advantage;               /* [R][T], already normalised (policy) */
+  const float *d_return;                  /* [R][T] (value) */
+  const int32_t *d_length;                /* [R] */
+  float penalty, kl_cutoff, kl_cutoff_coef;   /* the current KL penalty, kl_target * kl_cutoff_factor, kl_cutoff_coef (policy) */
+} RexPpoBatch;
+typedef struct RexPpoGrad {               /* the gradients, shaped like RexPpoNet's tensors: they can BE the parameters' .grad */
+  float *d_w1, *d_b1, *d_w2, *d_b2, *d_w3, *d_b3, *d_logstd;
+} RexPpoGrad;
+/* Bytes of workspace the two loss calls below need for a memory of `rows` x `steps` (< 0: unsupported shape).  16-byte aligned. */
+REX_API long long rex_ppo_workspace_bytes(int rows, int steps, int obs_dim, int out_dim, int hidden1, int hidden2);
+/* utility.py:71-81 and 97-110, one launch, one lane per row, a reverse scan.  With m_t = [t < length]:
+ *   return_t = m_t reward_t + discount return_{t+1}                                                       -> d_return (nullable)
+ *   lambda_t = m_t reward_t + discount (1 - lambda) value_t + m_t discount lambda lambda_{t+1}            -> d_lambda_return (with d_value) */
+REX_API int rex_ppo_returns(int rows, int steps, const float* d_reward, const int32_t* d_length, float discount, float* d_return,
+                            const float* d_value, float lambda, float* d_lambda_return, void* stream);
+/* The policy loss of algorithm.py:376-434.  With KL_t = diag_normal_kl(old || new) (utility.py:127-132), logp = diag_normal_logpdf AS
+ * WRITTEN in utility.py:135-139 (-0.5 (log 2 pi + logstd) - 0.5 ((x - mean) / e^logstd)^2 summed: its -0.5 logstd term kept),
+ * ratio_t = exp(logp_new - logp_old), kl_r = (1/T) sum_t m_t KL_t and c = kl_cutoff:
+ *   loss = (1/R) sum_r [ -(1/T) sum_t m_t ratio_t adv_t + penalty kl_r + coef [kl_r > c] (kl_r - c)^2 ]
+ * (T is the padded step count: the reference's reduce_mean runs over the padded axis.)  Backward seeds of a valid step, l = logstd:
+ *   w_r = penalty + 2 coef [kl_r > c] (kl_r - c)
+ *   dKL/dm = (m - m0) / e^2l          dKL/dl   = 1 - e^(2 l0 - 2 l) - (m - m0)^2 / e^2l
+ *   dlogp/dm = (x - m) / e^2l         dlogp/dl = -0.5 + ((x - m) / e^l)^2
+ *   g_m = (-ratio adv dlogp/dm + w_r dKL/dm) / (R T), g_l likewise, g_z = g_m (1 - m^2)
+ * d_loss [1] and d_kl_row [R] are always written; grad == NULL makes the call forward-only (the same loss and kl_row, bit for bit).
+ * Launches on `stream`, no host synchronisation. */
+REX_API int rex_ppo_policy_loss(const RexPpoNet* net, const RexPpoBatch* batch, const RexPpoGrad* grad, float* d_loss, float* d_kl_row,
+                                void* d_workspace, void* stream);
+/* The value loss of algorithm.py:289-301: loss = (1 / (R T)) sum 0.5 m_t (return_t - value_t)^2 and the gradients of the value net's six
+ * tensors (grad->d_logstd is ignored; grad == NULL: forward-only).  d_value_out (nullable): [R][T], the masked values, zero beyond the length. */
+REX_API int rex_ppo_value_loss(const RexPpoNet* net, const RexPpoBatch* batch, const RexPpoGrad* grad, float* d_loss, float* d_value_out,
+                               void* d_workspace, void* stream);
+
 REX_API const char* rex_last_error(void);
 REX_API int rex_abi_version(void);
 

@@ -72,6 +72,27 @@ class RexCamera(ctypes.Structure):
                 ("fov_deg", ctypes.c_float), ("near_plane", ctypes.c_float), ("far_plane", ctypes.c_float)]
 
 
+class RexPpoNet(ctypes.Structure):
+    """Mirror of `struct RexPpoNet` (include/rexsim.h): a two-layer ReLU network of the fused learner, torch layout."""
+    _fields_ = [("obs_dim", ctypes.c_int32), ("out_dim", ctypes.c_int32), ("hidden1", ctypes.c_int32), ("hidden2", ctypes.c_int32),
+                ("d_w1", ctypes.c_void_p), ("d_b1", ctypes.c_void_p), ("d_w2", ctypes.c_void_p), ("d_b2", ctypes.c_void_p),
+                ("d_w3", ctypes.c_void_p), ("d_b3", ctypes.c_void_p), ("d_logstd", ctypes.c_void_p)]
+
+
+class RexPpoBatch(ctypes.Structure):
+    """Mirror of `struct RexPpoBatch` (include/rexsim.h): the episode memory one loss call runs over."""
+    _fields_ = [("rows", ctypes.c_int32), ("steps", ctypes.c_int32), ("d_observ", ctypes.c_void_p),
+                ("d_action", ctypes.c_void_p), ("d_old_mean", ctypes.c_void_p), ("d_old_logstd", ctypes.c_void_p),
+                ("d_advantage", ctypes.c_void_p), ("d_return", ctypes.c_void_p), ("d_length", ctypes.c_void_p),
+                ("penalty", ctypes.c_float), ("kl_cutoff", ctypes.c_float), ("kl_cutoff_coef", ctypes.c_float)]
+
+
+class RexPpoGrad(ctypes.Structure):
+    """Mirror of `struct RexPpoGrad` (include/rexsim.h): where the gradients go, shaped like the network's tensors."""
+    _fields_ = [("d_w1", ctypes.c_void_p), ("d_b1", ctypes.c_void_p), ("d_w2", ctypes.c_void_p), ("d_b2", ctypes.c_void_p),
+                ("d_w3", ctypes.c_void_p), ("d_b3", ctypes.c_void_p), ("d_logstd", ctypes.c_void_p)]
+
+
 class RexSimError(RuntimeError):
     pass
 
@@ -126,6 +147,13 @@ _SIGS = {
                                 ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p], ctypes.c_int),
     "rex_render_visual": ([ctypes.c_void_p, ctypes.POINTER(RexCamera), ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                            ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p], ctypes.c_int),
+    "rex_ppo_workspace_bytes": ([ctypes.c_int] * 6, ctypes.c_longlong),
+    "rex_ppo_returns": ([ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_float, ctypes.c_void_p, ctypes.c_void_p,
+                         ctypes.c_float, ctypes.c_void_p, ctypes.c_void_p], ctypes.c_int),
+    "rex_ppo_policy_loss": ([ctypes.POINTER(RexPpoNet), ctypes.POINTER(RexPpoBatch), ctypes.POINTER(RexPpoGrad), ctypes.c_void_p, ctypes.c_void_p,
+                             ctypes.c_void_p, ctypes.c_void_p], ctypes.c_int),
+    "rex_ppo_value_loss": ([ctypes.POINTER(RexPpoNet), ctypes.POINTER(RexPpoBatch), ctypes.POINTER(RexPpoGrad), ctypes.c_void_p, ctypes.c_void_p,
+                            ctypes.c_void_p, ctypes.c_void_p], ctypes.c_int),
     "rex_last_error": ([], ctypes.c_char_p),
     "rex_abi_version": ([], ctypes.c_int),
 }

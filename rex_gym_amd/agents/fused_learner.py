@@ -1,0 +1,180 @@
+"""The fused PPO learner: `PPOConfig(learner="fused")` runs the losses of agents/ppo.py and their parameter gradients in the HIP
+kernels of csrc/rex_learner.h (rex_ppo_policy_loss, rex_ppo_value_loss, rex_ppo_returns; formulas in include/rexsim.h) instead of
+PyTorch autograd.  Adam, the gradient all-reduce (`PPOAgent._sync`), the filters and the penalty adaptation stay in PyTorch: the kernels
+write the gradients straight into the tensors that ARE the parameters' `.grad`.
+
+Host-only pieces (no GPU needed): `output_seeds`, the hand-derived backward seeds of the policy loss in plain torch -- what the kernel
+computes per sample, checked against autograd in tests/test_fused_learner_host.py -- and `flat_gradients` / `net_struct` / `grad_struct`,
+which lay parameters and gradients out for the C ABI.
+"""
+import ctypes
+
+import torch
+
+from .. import _lib
+
+
+def output_seeds(mean, logstd, old_mean, old_logstd, action, advantage, length, penalty, cutoff, coef):
+    """d loss / d mean, d loss / d logstd (both [R, T, A]) and kl_row [R] of `_update_policy`'s loss, derived by hand:
+
+        loss = (1/R) sum_r [ -(1/T) sum_t m ratio adv + penalty kl_r + coef [kl_r > c] (kl_r - c)^2 ],  kl_r = (1/T) sum_t m KL_t
+        w_r = penalty + 2 coef [kl_r > c] (kl_r - c)
+        dKL/dm = (m - m0) / e^2l         dKL/dl   = 1 - e^(2 l0 - 2 l) - (m - m0)^2 / e^2l
+        dlogp/dm = (x - m) / e^2l        dlogp/dl = -0.5 + ((x - m) / e^l)^2      (diag_normal_logpdf as written: its -0.5 logstd)
+        g = (-ratio adv dlogp + w_r dKL) / (R T) on valid steps, 0 on padded ones
+
+    mean, logstd, old_mean, old_logstd, action: [R, T, A]; advantage: [R, T]; length: [R]."""
+    R, T, _ = mean.shape
+    mask = (torch.arange(T, device=mean.device)[None, :] < length[:, None]).to(mean.dtype)
+    ie2 = torch.exp(-2 * logstd)
+    dm, dx = mean - old_mean, action - mean
+    ev = torch.exp(2 * old_logstd - 2 * logstd)
+    kl_t = 0.5 * (ev + dm ** 2 * ie2 + 2 * logstd - 2 * old_logstd - 1).sum(-1)
+    kl_row = (mask * kl_t).mean(1)
+    u2, u02 = (dx * torch.exp(-logstd)) ** 2, ((action - old_mean) * torch.exp(-old_logstd)) ** 2
+    ratio = torch.exp((-0.5 * (logstd - old_logstd) - 0.5 * (u2 - u02)).sum(-1))
+    w = penalty + 2 * coef * (kl_row > cutoff).to(mean.dtype) * (kl_row - cutoff)
+    ra = (mask * ratio * advantage)[..., None]
+    wk = (mask * w[:, None])[..., None]
+    g_mean = (wk * dm * ie2 - ra * dx * ie2) / (R * T)
+    g_logstd = (wk * (1 - ev - dm ** 2 * ie2) - ra * (-0.5 + u2)) / (R * T)
+    return g_mean, g_logstd, kl_row
+
+
+def flat_gradients(params):
+    """One flat float32 buffer on the parameters' device, and every parameter's `.grad` set to its own view into it (torch layout, the
+    order of `params`): the kernels write the gradients where Adam and the all-reduce read them.  Returns (flat, views)."""
+    params = list(params)
+    flat = torch.zeros(sum(p.numel() for p in params), dtype=torch.float32, device=params[0].device)
+    views, at = [], 0
+    for p in params:
+        if p.dtype != torch.float32 or not p.is_contiguous():
+            raise ValueError("the fused learner needs contiguous float32 parameters")
+        v = flat[at:at + p.numel()].view(p.shape)
+        p.grad = v
+        views.append(v)
+        at += p.numel()
+    return flat, views
+
+
+def _tensors_struct(cls, tensors):
+    """w1, b1, w2, b2, w3, b3 (and logstd) -> the d_* pointer fields of a RexPpoNet / RexPpoGrad"""
+    names = ("d_w1", "d_b1", "d_w2", "d_b2", "d_w3", "d_b3", "d_logstd")
+    if len(tensors) not in (6, 7):
+        raise ValueError("a two-layer network has six tensors (and logstd): W1, b1, W2, b2, W3, b3")
+    s = cls()
+    for n, t in zip(names, tensors):
+        setattr(s, n, t.data_ptr())
+    return s
+
+
+def net_struct(params):
+    """RexPpoNet of a network given as its tensors in torch order and layout: Linear weights [out][in] as they are."""
+    params = list(params)
+    s = _tensors_struct(_lib.RexPpoNet, params)
+    w1, w2, w3 = params[0], params[2], params[4]
+    if w2.shape[1] != w1.shape[0] or w3.shape[1] != w2.shape[0] or any(params[2 * k + 1].shape != (params[2 * k].shape[0],) for k in range(3)):
+        raise ValueError("the tensors are not a chain of three Linear layers")
+    s.hidden1, s.obs_dim = w1.shape
+    s.hidden2 = w2.shape[0]
+    s.out_dim = w3.shape[0]
+    return s
+
+
+def grad_struct(views):
+    return _tensors_struct(_lib.RexPpoGrad, list(views))
+
+
+def check_config(cfg, device):
+    """What PPOConfig(learner="fused") needs; raises ValueError otherwise (PPOAgent.__init__)."""
+    if cfg.network != "forward":
+        raise ValueError("PPOConfig(learner='fused') is the ForwardGaussianPolicy's learner (network='forward'); the recurrent policy's update is "
+                         "out of its scope and stays on learner='autograd'")
+    if len(cfg.policy_layers) != 2 or len(cfg.value_layers) != 2:
+        raise ValueError("PPOConfig(learner='fused') needs two policy layers and two value layers (the shape of every shipped config)")
+    if torch.device(device).type != "cuda":
+        raise ValueError("PPOConfig(learner='fused') runs HIP kernels: it needs a CUDA/HIP device, not %r" % (str(device),))
+
+
+class FusedLearner:
+    """The kernels behind a PPOAgent: owns the flat gradient buffers (every parameter's .grad is a view into them), the workspace and the
+    int32 copy of the memory's lengths.  Every call launches on the current stream and does not synchronise with the host."""
+
+    def __init__(self, net, rows, steps, device):
+        self.device = torch.device(device)
+        self.rows, self.steps = int(rows), int(steps)
+        self.policy_params, self.value_params = net.policy_parameters(), net.value_parameters()
+        self.policy_flat, self.policy_grads = flat_gradients(self.policy_params)
+        self.value_flat, self.value_grads = flat_gradients(self.value_params)
+        self._L = _lib.lib()
+        need = 0
+        for params in (self.policy_params, self.value_params):
+            n = net_struct(params)
+            b = self._L.rex_ppo_workspace_bytes(self.rows, self.steps, n.obs_dim, n.out_dim, n.hidden1, n.hidden2)
+            if b < 0:
+                raise ValueError("the fused learner does not offer this shape: " + self._L.rex_last_error().decode("utf-8", "replace"))
+            need = max(need, b)
+        self.workspace = torch.empty(need // 4, dtype=torch.float32, device=self.device)
+        self.length = torch.zeros(self.rows, dtype=torch.int32, device=self.device)
+        self.kl_row = torch.zeros(self.rows, device=self.device)
+        self._scratch_loss = torch.zeros(1, device=self.device)
+
+    def _stream(self):
+        return ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+    def _batch(self, observ, **blocks):
+        b = _lib.RexPpoBatch()
+        b.rows, b.steps = self.rows, self.steps
+        if observ.shape[:2] != (self.rows, self.steps):
+            raise ValueError("the memory is %s, the learner was made for %d x %d" % (tuple(observ.shape[:2]), self.rows, self.steps))
+        keep = [observ.contiguous()]
+        b.d_observ, b.d_length = keep[0].data_ptr(), self.length.data_ptr()
+        for name, t in blocks.items():
+            t = t.contiguous()
+            keep.append(t)
+            setattr(b, "d_" + name, t.data_ptr())
+        return b, keep
+
+    def set_length(self, length):
+        self.length.copy_(length)
+        return self.length
+
+    def returns(self, reward, discount, value=None, lambda_=None):
+        """discounted_return, and lambda_return when a value block is given: (return, lambda_return or None)"""
+        reward = reward.contiguous()
+        ret = torch.empty_like(reward)
+        lam = torch.empty_like(reward) if value is not None else None
+        value = value.contiguous() if value is not None else None
+        with torch.cuda.device(self.device):
+            _lib.check(self._L.rex_ppo_returns(reward.shape[0], reward.shape[1], reward.data_ptr(), self.length.data_ptr(), float(discount), ret.data_ptr(),
+                                               value.data_ptr() if value is not None else None, float(lambda_ or 0.0),
+                                               lam.data_ptr() if lam is not None else None, self._stream()), "rex_ppo_returns")
+        return ret, lam
+
+    def policy_loss(self, observ, action, old_mean, old_logstd, advantage, penalty, cutoff, coef, loss_out=None, grad=True):
+        """One epoch's policy loss into loss_out[0] (a device tensor), the rows' KL into self.kl_row, the gradients into the .grad views."""
+        b, keep = self._batch(observ, action=action, old_mean=old_mean, old_logstd=old_logstd, advantage=advantage)
+        b.penalty, b.kl_cutoff, b.kl_cutoff_coef = float(penalty), float(cutoff), float(coef)
+        loss_out = self._scratch_loss if loss_out is None else loss_out
+        net, g = net_struct(self.policy_params), grad_struct(self.policy_grads)
+        with torch.cuda.device(self.device):
+            _lib.check(self._L.rex_ppo_policy_loss(ctypes.byref(net), ctypes.byref(b), ctypes.byref(g) if grad else None, loss_out.data_ptr(),
+                                                   self.kl_row.data_ptr(), self.workspace.data_ptr(), self._stream()), "rex_ppo_policy_loss")
+        return loss_out, self.kl_row
+
+    def value_loss(self, observ, return_, loss_out=None, grad=True, value_out=None):
+        """One epoch's value loss into loss_out[0], the gradients into the .grad views; value_out [R, T]: the masked values."""
+        b, keep = self._batch(observ, **{"return": return_})
+        loss_out = self._scratch_loss if loss_out is None else loss_out
+        net, g = net_struct(self.value_params), grad_struct(self.value_grads)
+        with torch.cuda.device(self.device):
+            _lib.check(self._L.rex_ppo_value_loss(ctypes.byref(net), ctypes.byref(b), ctypes.byref(g) if grad else None, loss_out.data_ptr(),
+                                                  value_out.data_ptr() if value_out is not None else None, self.workspace.data_ptr(), self._stream()),
+                       "rex_ppo_value_loss")
+        return loss_out
+
+    def values(self, observ):
+        """The value net's forward pass over the memory, zero beyond every row's length (the advantage's baseline)."""
+        out = torch.empty((self.rows, self.steps), device=self.device)
+        self.value_loss(observ, torch.zeros_like(out), grad=False, value_out=out)     # (the return block only feeds the loss, which is dropped)
+        return out

@@ -1,4 +1,6 @@
 """KL-penalty PPO of the reference (rex_gym/agents/ppo/algorithm.py, a TF1 graph) restated in PyTorch on the device.
+The update's losses and gradients run through PyTorch autograd (PPOConfig.learner = "autograd", the default) or, for the forward
+network, through the fused HIP kernels of csrc/rex_learner.h (learner = "fused", agents/fused_learner.py).
 
 The reference learner pulls numpy arrays out of N environment processes every step; here observations, rewards and
 done flags are the device tensors RexBatchEnv returns, the episode buffers live in HBM and nothing crosses PCIe.
@@ -43,6 +45,8 @@ class PPOConfig:
     kl_init_penalty: float = 1.0
     max_length: int = 2000
     network: str = "forward"        # "forward": ForwardGaussianPolicy (every shipped config); "recurrent": RecurrentGaussianPolicy
+    learner: str = "autograd"       # "autograd": the losses below through PyTorch autograd; "fused": the HIP kernels of csrc/rex_learner.h
+                                    # (agents/fused_learner.py: forward network, two + two layers, a HIP device)
 
 
 class StreamingNormalize:
@@ -255,6 +259,11 @@ class PPOAgent:
     def __init__(self, num_agents, obs_dim, action_dim, cfg=None, device="cuda", seed=0, sync_gradients=False):
         self.cfg = cfg = cfg or PPOConfig()
         self.n, self.device = num_agents, torch.device(device)
+        if cfg.learner not in ("autograd", "fused"):
+            raise ValueError("PPOConfig.learner must be 'autograd' or 'fused'")
+        if cfg.learner == "fused":
+            from .fused_learner import check_config
+            check_config(cfg, self.device)
         gen = torch.Generator(device="cpu"); gen.manual_seed(seed)
         with torch.random.fork_rng(devices=[]):
             torch.manual_seed(seed)
@@ -277,6 +286,10 @@ class PPOAgent:
         self.policy_opt = torch.optim.Adam(self.net.policy_parameters(), lr=cfg.policy_lr, eps=1e-8)
         self.value_opt = torch.optim.Adam(self.net.value_parameters(), lr=cfg.value_lr, eps=1e-8)
         self.sync_gradients = sync_gradients
+        self._fused = None
+        if cfg.learner == "fused":
+            from .fused_learner import FusedLearner
+            self._fused = FusedLearner(self.net, cfg.update_every, T, self.device)
         self._full_episodes_unpolled, self._warned_unpolled = 0, False
         self.last = None
         self.updates = 0
@@ -383,6 +396,8 @@ class PPOAgent:
                     p.grad /= world
 
     def _update_value(self, observ, reward, length):
+        if self._fused is not None:
+            return self._update_value_fused(observ, reward, length)
         mask = _mask(length, reward.shape[1])
         return_ = discounted_return(reward, length, self.cfg.discount)
         losses = []
@@ -396,7 +411,43 @@ class PPOAgent:
             losses.append(loss.detach())
         return {"value_loss": float(torch.stack(losses).mean())}
 
+    # ---- the same three steps on the fused learner (cfg.learner == "fused"): the kernels compute what the autograd lines compute ----
+    @torch.no_grad()
+    def _update_value_fused(self, observ, reward, length):
+        fl = self._fused
+        fl.set_length(length)
+        return_, _ = fl.returns(reward, self.cfg.discount)
+        losses = torch.zeros(self.cfg.update_epochs_value, device=self.device)
+        params = self.net.value_parameters()
+        for e in range(self.cfg.update_epochs_value):
+            fl.value_loss(observ, return_, losses[e:e + 1])
+            self._sync(params)
+            self.value_opt.step()
+        return {"value_loss": float(losses.mean())}
+
+    @torch.no_grad()
+    def _update_policy_fused(self, observ, action, old_mean, old_logstd, reward, length):
+        cfg, fl = self.cfg, self._fused
+        fl.set_length(length)
+        return_, _ = fl.returns(reward, cfg.discount)
+        value = fl.values(observ)
+        if cfg.gae_lambda:
+            advantage = fl.returns(reward, cfg.discount, value, cfg.gae_lambda)[1]
+        else:
+            advantage = return_ - value
+        advantage = (advantage - advantage.mean()) / (advantage.var(unbiased=False).sqrt() + 1e-8)
+        losses = torch.zeros(cfg.update_epochs_policy, device=self.device)
+        params = self.net.policy_parameters()
+        for e in range(cfg.update_epochs_policy):
+            fl.policy_loss(observ, action, old_mean, old_logstd, advantage, self.penalty, cfg.kl_target * cfg.kl_cutoff_factor, cfg.kl_cutoff_coef,
+                           losses[e:e + 1])
+            self._sync(params)
+            self.policy_opt.step()
+        return {"policy_loss": float(losses.mean()), "return": float(return_[:, 0].mean())}
+
     def _update_policy(self, observ, action, old_mean, old_logstd, reward, length):
+        if self._fused is not None:
+            return self._update_policy_fused(observ, action, old_mean, old_logstd, reward, length)
         cfg = self.cfg
         with torch.no_grad():
             return_ = discounted_return(reward, length, cfg.discount)
@@ -429,8 +480,14 @@ class PPOAgent:
     @torch.no_grad()
     def _adjust_penalty(self, observ, old_mean, old_logstd, length):
         """algorithm.py:436-474: x1.5 when the policy moved more than 1.3 kl_target, /1.5 below 0.7 kl_target."""
-        mean, logstd, _ = self.net(observ)
-        kl = (_mask(length, observ.shape[1]) * diag_normal_kl(old_mean, old_logstd, mean, logstd)).mean()
+        if self._fused is not None:     # the forward-only mode of the policy kernel: kl_row [R], its mean is the mean over R x T
+            # (only kl_row is used: old_mean stands in for the action block and the advantage is zero, so the call's LOSS is meaningless -- NaN
+            # where a ratio overflows, inf x 0 -- and is dropped)
+            self._fused.set_length(length)
+            kl = self._fused.policy_loss(observ, old_mean, old_mean, old_logstd, torch.zeros_like(old_mean[..., 0]), 0.0, 0.0, 0.0, grad=False)[1].mean()
+        else:
+            mean, logstd, _ = self.net(observ)
+            kl = (_mask(length, observ.shape[1]) * diag_normal_kl(old_mean, old_logstd, mean, logstd)).mean()
         if self._distributed():               # one penalty for all ranks: the mean KL over every rank's memory
             torch.distributed.all_reduce(kl)
             kl = kl / torch.distributed.get_world_size()
@@ -593,6 +650,8 @@ if __name__ == "__main__":   # python -m rex_gym_amd.agents.ppo --task walk --en
     ap.add_argument("--segment", type=int, default=25)
     ap.add_argument("--network", default="forward", choices=["forward", "recurrent"],
                     help="forward: ForwardGaussianPolicy (every shipped config); recurrent: RecurrentGaussianPolicy, a GRU cell as the last policy layer")
+    ap.add_argument("--learner", default="autograd", choices=["autograd", "fused"],
+                    help="autograd: the update through PyTorch autograd; fused: the HIP loss / gradient kernels (agents/fused_learner.py; forward network only)")
     ap.add_argument("--toe-friction", type=float, default=None, help="pin the toe friction (RexBatchEnv(friction_range=(f, f))); the standup task matches its "
                                                                      "PyBullet record at 0.25 (DESIGN.md section 2)")
     ap.add_argument("--logdir", default=None, help="write the trained policy there as a TensorFlow-1 checkpoint the reference's policy player "
@@ -603,7 +662,7 @@ if __name__ == "__main__":   # python -m rex_gym_amd.agents.ppo --task walk --en
     env = RexBatchEnv(a.envs, task=a.task, signal_type=a.signal, seed=a.seed, max_episode_steps=a.max_length, range_normalize=True,
                       gait_clock_scale=a.gait_clock_scale, auto_reset=a.loop == "segments", check_actions=False,
                       **({"friction_range": (a.toe_friction, a.toe_friction)} if a.toe_friction is not None else {}))
-    agent = PPOAgent(a.envs, env.obs_dim, env.action_dim, PPOConfig(update_every=a.envs, max_length=a.max_length, network=a.network), seed=a.seed)
+    agent = PPOAgent(a.envs, env.obs_dim, env.action_dim, PPOConfig(update_every=a.envs, max_length=a.max_length, network=a.network, learner=a.learner), seed=a.seed)
     actor = None
     if a.loop == "segments":
         from .fused_actor import FusedActor

@@ -6,6 +6,7 @@
 #include "rex_kernels.h"
 #include "rex_render.h"
 #include "rex_visual_gen.h"
+#include "rex_learner.h"
 #include <algorithm>
 #include <cstdarg>
 #include <cstring>
@@ -1221,6 +1222,113 @@ int rex_gait_loop(int n, int mode, double* d_planner, const double* d_params, fl
   hipLaunchKernelGGL(rex::rex_gait_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, n, mode, d_planner, d_params, d_frames_out);
   HIPCHK(hipGetLastError());
   return REX_OK;
+}
+
+// ---- the fused PPO learner (rex_learner.h) ----
+static int ppo_check(const char* who, const RexPpoNet* net, const RexPpoBatch* b, bool value) {
+  if (!net || !b) return failf(REX_EINVAL, "%s: null pointer", who);
+  const int O = net->obs_dim, A = net->out_dim;
+  if (O != 4 && O != 16 && O != 22) return failf(REX_EINVAL, "%s: obs_dim %d is not offered (4, 16 or 22)", who, O);
+  if (value ? A != 1 : (A != 1 && A != 2 && A != 4 && A != 8))
+    return failf(REX_EINVAL, "%s: out_dim %d is not offered (%s)", who, A, value ? "the value net has one output" : "action_dim 1, 2, 4 or 8");
+  if (net->hidden1 < 1 || net->hidden1 > REX_PPO_MAX_H1 || net->hidden2 < 1 || net->hidden2 > REX_PPO_MAX_H2)
+    return failf(REX_EINVAL, "%s: hidden layers of %d and %d units are not offered (1..%d and 1..%d)", who, net->hidden1, net->hidden2, REX_PPO_MAX_H1, REX_PPO_MAX_H2);
+  if (b->rows < 1 || b->steps < 1 || (long long)b->rows * b->steps * 24 >= (1ll << 31))
+    return failf(REX_EINVAL, "%s: a memory of %d rows x %d steps is not offered (rows, steps >= 1, rows * steps * 24 < 2^31)", who, b->rows, b->steps);
+  if (!net->d_w1 || !net->d_b1 || !net->d_w2 || !net->d_b2 || !net->d_w3 || !net->d_b3 || (!value && !net->d_logstd)) return failf(REX_EINVAL, "%s: null weight pointer", who);
+  if (!b->d_observ || !b->d_length || (value ? !b->d_return : (!b->d_action || !b->d_old_mean || !b->d_old_logstd || !b->d_advantage)))
+    return failf(REX_EINVAL, "%s: null memory block", who);
+  return REX_OK;
+}
+
+static int ppo_loss(const char* who, bool value, const RexPpoNet* net, const RexPpoBatch* b, const RexPpoGrad* grad, float* d_loss, float* d_kl_row, float* d_value_out,
+                    void* d_workspace, hipStream_t st) {
+  const int rc = ppo_check(who, net, b, value);
+  if (rc != REX_OK) return rc;
+  if (!d_loss || !d_workspace || (!value && !d_kl_row)) return failf(REX_EINVAL, "%s: null output or workspace pointer", who);
+  if (grad && (!grad->d_w1 || !grad->d_b1 || !grad->d_w2 || !grad->d_b2 || !grad->d_w3 || !grad->d_b3 || (!value && !grad->d_logstd)))
+    return failf(REX_EINVAL, "%s: null gradient pointer (pass grad = NULL for a forward-only call)", who);
+  const int O = net->obs_dim, A = net->out_dim, H1 = net->hidden1, H2 = net->hidden2, R = b->rows, T = b->steps;
+  const rex::PpoWs ws = rex::ppo_workspace(R, T, O, A, H1, H2);
+  float* w = static_cast<float*>(d_workspace);
+  rex::PpoArgs a{};
+  a.w1 = net->d_w1; a.b1 = net->d_b1; a.b2 = net->d_b2; a.w3 = net->d_w3; a.b3 = net->d_b3; a.logstd = net->d_logstd;
+  a.w2p = w + ws.w2p; a.w2t = w + ws.w2t; a.part = w + ws.part; a.pgrad = w + ws.pgrad;
+  a.observ = b->d_observ; a.action = b->d_action; a.old_mean = b->d_old_mean; a.old_logstd = b->d_old_logstd;
+  a.target = value ? b->d_return : b->d_advantage;
+  a.length = b->d_length; a.kl_row = d_kl_row; a.value_out = d_value_out;
+  a.O = O; a.A = A; a.H1 = H1; a.H2 = H2; a.H1p = rex::ppo_up(H1, 32); a.H2p = rex::ppo_up(H2, 32); a.R = R; a.T = T; a.NT = ws.ntiles;
+  a.penalty = b->penalty; a.cutoff = b->kl_cutoff; a.coef = b->kl_cutoff_coef;
+  a.inv_rt = (float)(1.0 / ((double)R * (double)T));
+  const int OP = O == 22 ? 24 : O;
+  const size_t lds = sizeof(float) * (size_t)rex::ppo_lds_floats(OP, a.H1p, a.H2p);
+  auto launch = [&](rex::PpoTileKernel k) -> hipError_t {
+    // more than 64 KB of dynamic LDS needs the function's limit raised: once per (kernel, device) and size, not per launch
+    struct Raised { rex::PpoTileKernel k; int device; size_t bytes; };
+    static thread_local std::vector<Raised> raised;
+    int device = 0;
+    hipError_t e = hipGetDevice(&device);
+    if (e != hipSuccess) return e;
+    auto it = std::find_if(raised.begin(), raised.end(), [&](const Raised& r) { return r.k == k && r.device == device; });
+    if (it == raised.end() || it->bytes < lds) {
+      e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+      if (e != hipSuccess) return e;
+      if (it == raised.end()) raised.push_back({k, device, lds}); else it->bytes = lds;
+    }
+    hipLaunchKernelGGL(k, dim3(ws.groups), dim3(REX_PPO_THREADS), lds, st, a);
+    return hipGetLastError();
+  };
+  hipLaunchKernelGGL(rex::rex_ppo_pack_kernel, dim3((a.H1p * a.H2p + 255) / 256), dim3(256), 0, st, net->d_w2, H1, H2, a.H1p, a.H2p, w + ws.w2p, w + ws.w2t);
+  HIPCHK(hipGetLastError());
+  if (value) {
+    // one pass: the tiles' loss terms come out of the same pass as the gradients (tiles beyond a row's length are skipped: their values are zero)
+    if (d_value_out) HIPCHK(hipMemsetAsync(d_value_out, 0, sizeof(float) * (size_t)R * T, st));
+    HIPCHK(launch(grad ? rex::ppo_tile_kernel<true, true>(OP) : rex::ppo_tile_kernel<true, false>(OP)));
+    hipLaunchKernelGGL(rex::rex_ppo_rows_kernel<true>, dim3(1), dim3(REX_PPO_THREADS), 0, st, a, d_loss, (float*)nullptr);
+    HIPCHK(hipGetLastError());
+  } else {
+    // two phases: w_r of the seeds needs the whole row's KL -- forward only (loss, kl_row), then forward + backward
+    HIPCHK(launch(rex::ppo_tile_kernel<false, false>(OP)));
+    hipLaunchKernelGGL(rex::rex_ppo_rows_kernel<false>, dim3(1), dim3(REX_PPO_THREADS), 0, st, a, d_loss, d_kl_row);
+    HIPCHK(hipGetLastError());
+    if (grad) HIPCHK(launch(rex::ppo_tile_kernel<false, true>(OP)));
+  }
+  if (grad) {
+    const rex::PpoOff o = rex::ppo_offsets(O, A, H1, H2);
+    const int np = value ? o.logstd : o.logstd + A;
+    const rex::PpoGradDev g{grad->d_w1, grad->d_b1, grad->d_w2, grad->d_b2, grad->d_w3, grad->d_b3, grad->d_logstd};
+    hipLaunchKernelGGL(rex::rex_ppo_reduce_kernel, dim3((np + 255) / 256), dim3(256), 0, st, (const float*)(w + ws.pgrad), ws.groups, o, np, g);
+    HIPCHK(hipGetLastError());
+  }
+  return REX_OK;
+}
+
+long long rex_ppo_workspace_bytes(int rows, int steps, int obs_dim, int out_dim, int hidden1, int hidden2) {
+  RexPpoNet net{}; RexPpoBatch b{};
+  net.obs_dim = obs_dim; net.out_dim = out_dim; net.hidden1 = hidden1; net.hidden2 = hidden2; b.rows = rows; b.steps = steps;
+  const float one = 0.0f; const int32_t len = 0;      // (the shape checks only: any non-null pointer passes the null checks)
+  net.d_w1 = net.d_b1 = net.d_w2 = net.d_b2 = net.d_w3 = net.d_b3 = net.d_logstd = &one;
+  b.d_observ = b.d_action = b.d_old_mean = b.d_old_logstd = b.d_advantage = b.d_return = &one; b.d_length = &len;
+  if (ppo_check("rex_ppo_workspace_bytes", &net, &b, false) != REX_OK) return REX_EINVAL;
+  return (long long)(sizeof(float) * rex::ppo_workspace(rows, steps, obs_dim, out_dim, hidden1, hidden2).total);
+}
+
+int rex_ppo_returns(int rows, int steps, const float* d_reward, const int32_t* d_length, float discount, float* d_return, const float* d_value, float lambda,
+                    float* d_lambda_return, void* stream) {
+  if (rows < 1 || steps < 1 || (long long)rows * steps >= (1ll << 31) || !d_reward || !d_length || (!d_return && !d_lambda_return) || (d_lambda_return && !d_value))
+    return fail(REX_EINVAL, "rex_ppo_returns: bad arguments (rows, steps >= 1, rows * steps < 2^31, an output, d_value with d_lambda_return)%s", "");
+  hipLaunchKernelGGL(rex::rex_ppo_returns_kernel, dim3((rows + 63) / 64), dim3(64), 0, (hipStream_t)stream, rows, steps, d_reward, d_length, discount, d_return, d_value,
+                     lambda, (float)(1.0 - (double)lambda), d_lambda_return);
+  HIPCHK(hipGetLastError());
+  return REX_OK;
+}
+
+int rex_ppo_policy_loss(const RexPpoNet* net, const RexPpoBatch* batch, const RexPpoGrad* grad, float* d_loss, float* d_kl_row, void* d_workspace, void* stream) {
+  return ppo_loss("rex_ppo_policy_loss", false, net, batch, grad, d_loss, d_kl_row, nullptr, d_workspace, (hipStream_t)stream);
+}
+
+int rex_ppo_value_loss(const RexPpoNet* net, const RexPpoBatch* batch, const RexPpoGrad* grad, float* d_loss, float* d_value_out, void* d_workspace, void* stream) {
+  return ppo_loss("rex_ppo_value_loss", true, net, batch, grad, d_loss, nullptr, d_value_out, d_workspace, (hipStream_t)stream);
 }
 
 #ifdef REX_PROF   /* developer build only (tools/prof_sections.py): cycle counters of the sections of a substep */

@@ -1,0 +1,94 @@
+"""The host side of the fused PPO learner (agents/fused_learner.py, include/rexsim.h): the ABI surface, the config checks and the hand-derived
+backward seeds against autograd.  CPU only."""
+import os
+import re
+
+import pytest
+import torch
+
+from rex_gym_amd.agents import PPOAgent, PPOConfig
+from rex_gym_amd.agents import ppo
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+ENTRY_POINTS = ("rex_ppo_workspace_bytes", "rex_ppo_returns", "rex_ppo_policy_loss", "rex_ppo_value_loss")
+
+
+def test_the_abi_declares_binds_and_exports_the_learner():
+    from rex_gym_amd import _lib
+    hdr = open(os.path.join(ROOT, "include", "rexsim.h")).read()
+    declared = set(re.findall(r"REX_API\s+[\w\s\*]+?\b(rex_\w+)\s*\(", hdr))
+    assert set(ENTRY_POINTS) <= declared
+    assert set(ENTRY_POINTS) <= set(_lib.EXPORTED_SYMBOLS)
+    assert re.search(r"#define\s+REX_ABI_VERSION\s+6\b", hdr) and _lib.ABI_VERSION == 6
+    lib = _lib.lib()
+    for name in ENTRY_POINTS:
+        assert hasattr(lib, name)
+    assert lib.rex_abi_version() == 6
+    # the shape checks run on the host: the offered shapes have a workspace size, the others an error and a message
+    assert lib.rex_ppo_workspace_bytes(4096, 400, 4, 2, 200, 100) > 0
+    assert lib.rex_ppo_workspace_bytes(25, 2000, 22, 8, 256, 128) > 0
+    assert lib.rex_ppo_workspace_bytes(25, 2000, 5, 2, 200, 100) == -1 and b"obs_dim 5" in lib.rex_last_error()
+
+
+def test_the_learner_is_autograd_unless_asked_and_fused_states_what_it_needs():
+    assert PPOConfig().learner == "autograd"
+    with pytest.raises(ValueError, match="recurrent"):
+        PPOAgent(4, 4, 2, PPOConfig(learner="fused", network="recurrent"), device="cuda")
+    with pytest.raises(ValueError, match="two policy layers"):
+        PPOAgent(4, 4, 2, PPOConfig(learner="fused", policy_layers=(32,)), device="cuda")
+    with pytest.raises(ValueError, match="device"):
+        PPOAgent(4, 4, 2, PPOConfig(learner="fused"), device="cpu")
+    with pytest.raises(ValueError, match="learner"):
+        PPOAgent(4, 4, 2, PPOConfig(learner="triton"), device="cpu")
+
+
+def test_parameters_and_gradients_are_laid_out_for_the_abi():
+    from rex_gym_amd.agents.fused_learner import flat_gradients, grad_struct, net_struct
+    net = ppo.ForwardGaussianPolicy(16, 4, PPOConfig())
+    for params, out in ((net.policy_parameters(), 4), (net.value_parameters(), 1)):
+        flat, views = flat_gradients(params)
+        assert flat.numel() == sum(p.numel() for p in params)
+        at = 0
+        for p, v in zip(params, views):       # torch order, torch layout, back to back; the view IS the parameter's .grad
+            assert p.grad is v and v.shape == p.shape and v.data_ptr() == flat.data_ptr() + 4 * at
+            at += p.numel()
+        flat.fill_(2.0)
+        assert all(bool((p.grad == 2.0).all()) for p in params)
+        n, g = net_struct(params), grad_struct(views)
+        assert (n.obs_dim, n.out_dim, n.hidden1, n.hidden2) == (16, out, 200, 100)
+        assert n.d_w2 == params[2].data_ptr() and g.d_w2 == views[2].data_ptr() and g.d_b3 == views[5].data_ptr()
+        assert (n.d_logstd or 0) == (params[6].data_ptr() if len(params) == 7 else 0)
+    with pytest.raises(ValueError):
+        net_struct(net.policy_parameters()[:4])
+
+
+@pytest.mark.parametrize("O,A", [(4, 2), (16, 4), (4, 1), (4, 8)])
+def test_output_seeds_are_the_gradients_autograd_finds(O, A):
+    """d loss / d mean, d loss / d logstd and kl_row of the loss built exactly as `_update_policy` builds it, in fp64: rows above and below
+    the cutoff, a row of length 0 and a row of full length."""
+    from rex_gym_amd.agents.fused_learner import output_seeds
+    g = torch.Generator().manual_seed(11 + O + A)
+    R, T = 6, 9
+    length = torch.tensor([9, 0, 1, 5, 9, 7])
+    penalty, cutoff, coef = 0.7, 0.02, 1000.0
+    dt = torch.float64
+    mean = torch.tanh(torch.randn((R, T, A), generator=g, dtype=dt)).requires_grad_()
+    logstd = (-1.0 + 0.1 * torch.randn((R, T, A), generator=g, dtype=dt)).requires_grad_()
+    # rows 0-2 close to the old policy (small KL), rows 3-5 far from it (KL above the cutoff)
+    far = torch.tensor([0.01, 0.01, 0.01, 0.3, 0.3, 0.3], dtype=dt)[:, None, None]
+    old_mean = mean.detach() + far * torch.randn((R, T, A), generator=g, dtype=dt)
+    old_logstd = logstd.detach() + 0.1 * far * torch.randn((R, T, A), generator=g, dtype=dt)
+    action = old_mean + torch.exp(old_logstd) * torch.randn((R, T, A), generator=g, dtype=dt)
+    advantage = torch.randn((R, T), generator=g, dtype=dt)
+    mask = ppo._mask(length, T, dt)
+    kl = (mask * ppo.diag_normal_kl(old_mean, old_logstd, mean, logstd)).mean(1)
+    ratio = torch.exp(ppo.diag_normal_logpdf(mean, logstd, action) - ppo.diag_normal_logpdf(old_mean, old_logstd, action))
+    surrogate = -(mask * ratio * advantage).mean(1)
+    kl_cutoff = coef * (kl > cutoff).to(dt) * (kl - cutoff) ** 2
+    loss = (surrogate + penalty * kl + kl_cutoff).mean()
+    want_m, want_l = torch.autograd.grad(loss, (mean, logstd))
+    assert int((kl > cutoff).sum()) >= 1 and int(((kl <= cutoff) & (length > 0)).sum()) >= 1
+    g_m, g_l, kl_row = output_seeds(mean.detach(), logstd.detach(), old_mean, old_logstd, action, advantage, length, penalty, cutoff, coef)
+    for got, want in ((g_m, want_m), (g_l, want_l), (kl_row, kl.detach())):
+        assert float((got - want).abs().max()) <= 1e-10 * float(want.abs().max())
+    assert float(g_m[1].abs().sum()) == 0.0 and float(g_l[2, 1:].abs().sum()) == 0.0      # padded steps contribute exactly nothing

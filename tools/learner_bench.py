@@ -1,0 +1,129 @@
+"""Time one full PPO update (`PPOAgent._training()`) under each learner -- PyTorch autograd and the fused HIP kernels -- from the same memory
+contents, at the two shapes that matter:
+
+  walk4096   4 096 rows x 400 steps, O = 4, A = 2: the update of `python -m rex_gym_amd.agents.ppo --task walk --envs 4096 --max-length 400`
+  default25  25 rows x 2 000 steps: the reference's default update_every and max_length
+
+    python tools/learner_bench.py [--shapes walk4096,default25] [--runs 3] [--epochs 50]
+
+Every run starts from the same parameters, fresh Adam state and the same memory; one warm-up run, then the median of --runs runs.  The update is
+split into its phases with a device-synchronised wall clock around each: the policy epochs (with the advantage's value forward and
+normalisation), the value epochs, the return scans (both calls) and the penalty pass.  One JSON line per (shape, learner), then a summary line.
+Every episode is full length unless --short F makes a fraction F of the rows end early (uniform lengths: the fused kernels skip padded
+steps, autograd computes them); `valid` is the fraction of real steps."""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from rex_gym_amd.agents import PPOAgent, PPOConfig   # noqa: E402
+from rex_gym_amd.agents import ppo                   # noqa: E402
+
+SHAPES = {"walk4096": (4096, 400, 4, 2), "default25": (25, 2000, 4, 2)}
+
+
+def make_agent(shape, learner, epochs, short_fraction=0.0, seed=0):
+    R, T, O, A = SHAPES[shape]
+    cfg = PPOConfig(update_every=R, max_length=T, update_epochs_policy=epochs, update_epochs_value=epochs, learner=learner)
+    agent = PPOAgent(1, O, A, cfg, device="cuda", seed=seed)
+    g = torch.Generator().manual_seed(seed)
+    length = torch.full((R,), T, dtype=torch.long)
+    short = torch.rand(R, generator=g) < short_fraction
+    length[short] = torch.randint(1, T + 1, (int(short.sum()),), generator=g)
+    mask = ppo._mask(length, T)
+    observ = torch.randn((R, T, O), generator=g) * mask[..., None]
+    with torch.no_grad():
+        mean = agent.net(observ.cuda())[0].cpu() * mask[..., None]
+    logstd = torch.full((R, T, A), float(cfg.init_logstd)) * mask[..., None]
+    action = (mean + torch.exp(logstd) * torch.randn((R, T, A), generator=g)) * mask[..., None]
+    reward = torch.randn((R, T), generator=g) * mask
+    for dst, src in zip(agent.memory, (observ, action, mean, logstd, reward)):
+        dst.copy_(src)
+    agent.observ_filter.update(observ.reshape(-1, O)[:4096].cuda())
+    agent.reward_filter.update(reward.reshape(-1)[:4096].cuda())
+    return agent, length.cuda(), float(mask.mean())
+
+
+def timed_training(agent, length, saved):
+    """one _training() from the saved parameters; returns the phases' seconds"""
+    with torch.no_grad():
+        for p, q in zip(agent.net.parameters(), saved):
+            p.copy_(q)
+    agent.policy_opt.state.clear(); agent.value_opt.state.clear()
+    agent.penalty = float(agent.cfg.kl_init_penalty)
+    agent.memory_length.copy_(length)
+    agent.memory_index = agent.cfg.update_every
+    spans = {"policy": 0.0, "value": 0.0, "returns": 0.0, "penalty": 0.0}
+
+    def clock(fn, key, minus_returns=False):
+        def wrapped(*a, **k):
+            torch.cuda.synchronize()
+            before, t0 = spans["returns"], time.perf_counter()
+            out = fn(*a, **k)
+            torch.cuda.synchronize()
+            spans[key] += time.perf_counter() - t0 - ((spans["returns"] - before) if minus_returns else 0.0)
+            return out
+        return wrapped
+
+    restore = []
+
+    def patch(obj, name, key, minus=False):
+        orig = getattr(obj, name)
+        restore.append((obj, name, orig, name in vars(obj)))
+        setattr(obj, name, clock(orig, key, minus))
+
+    patch(agent, "_update_policy", "policy", True)
+    patch(agent, "_update_value", "value", True)
+    patch(agent, "_adjust_penalty", "penalty")
+    if agent._fused is not None:
+        patch(agent._fused, "returns", "returns")
+    else:
+        patch(ppo, "discounted_return", "returns")
+        patch(ppo, "lambda_return", "returns")
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    stats = agent._training()
+    torch.cuda.synchronize()
+    spans["total"] = time.perf_counter() - t0
+    for obj, name, orig, own in restore:
+        if own:
+            setattr(obj, name, orig)
+        else:
+            delattr(obj, name)
+    return spans, stats
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--shapes", default="walk4096,default25")
+    ap.add_argument("--learners", default="autograd,fused")
+    ap.add_argument("--runs", type=int, default=3)
+    ap.add_argument("--epochs", type=int, default=50)
+    ap.add_argument("--short", type=float, default=0.0, help="fraction of the rows whose episode ended early")
+    a = ap.parse_args()
+    summary = {}
+    for shape in a.shapes.split(","):
+        for learner in a.learners.split(","):
+            agent, length, valid = make_agent(shape, learner, a.epochs, a.short)
+            saved = [p.detach().clone() for p in agent.net.parameters()]
+            timed_training(agent, length, saved)                      # warm-up
+            runs = [timed_training(agent, length, saved) for _ in range(a.runs)]
+            med = {k: statistics.median(r[0][k] for r in runs) for k in runs[0][0]}
+            rec = {"shape": shape, "rows": SHAPES[shape][0], "steps": SHAPES[shape][1], "learner": learner, "epochs": a.epochs, "valid": round(valid, 4),
+                   "runs": a.runs, "median_s": {k: round(v, 5) for k, v in med.items()}, "total_s_runs": [round(r[0]["total"], 5) for r in runs],
+                   "stats": {k: runs[-1][1][k] for k in ("policy_loss", "value_loss", "kl_change")}}
+            print(json.dumps(rec), flush=True)
+            summary.setdefault(shape, {})[learner] = med["total"]
+            del agent
+            torch.cuda.empty_cache()
+    print(json.dumps({"summary_total_s": summary,
+                      "speedup": {s: round(v["autograd"] / v["fused"], 2) for s, v in summary.items() if "autograd" in v and "fused" in v}}), flush=True)
+
+
+if __name__ == "__main__":
+    main()
