@@ -544,6 +544,46 @@ REX_API int rex_ppo_policy_loss(const RexPpoNet* net, const RexPpoBatch* batch, 
 REX_API int rex_ppo_value_loss(const RexPpoNet* net, const RexPpoBatch* batch, const RexPpoGrad* grad, float* d_loss, float* d_value_out,
                                void* d_workspace, void* stream);
 
+/* ---- the fused RECURRENT PPO learner (csrc/rex_learner_rnn.h): the policy loss above for the RecurrentGaussianPolicy (networks.py:113-159)
+ * and its nine parameter gradients by backpropagation through time.  The value net of a recurrent agent is the plain two-layer network:
+ * rex_ppo_value_loss and rex_ppo_returns serve it unchanged.  For one episode row, h_0 = 0, o_t the filtered observation, F = hidden1, H = state:
+ *   x_t = relu(W1 o_t + b1)                                    W1 [F][O]
+ *   [r_t ; u_t] = sigmoid(Wg [x_t ; h_{t-1}] + bg)             Wg [2H][F+H], rows 0..H-1 = r, H..2H-1 = u
+ *   c_t = tanh(Wc [x_t ; r_t * h_{t-1}] + bc)                  Wc [H][F+H]
+ *   h_t = u_t h_{t-1} + (1 - u_t) c_t
+ *   m_t = tanh(Wm h_t + bm)                                    Wm [A][H];  logstd [A]
+ * Loss, kl_row and the seeds g_m, g_l, g_z = g_m (1 - m^2) of a valid step are rex_ppo_policy_loss's.  The backward recurrence, in reverse t
+ * with carry_T = 0:
+ *   dh   = Wm^T g_z,t + carry
+ *   du   = dh (h_{t-1} - c)      dc = dh (1 - u)       carry = dh u
+ *   da_c = dc (1 - c^2)          [dx_c ; drh] = Wc^T da_c
+ *   dr   = drh h_{t-1}           carry += drh r
+ *   da_g = [dr r (1 - r) ; du u (1 - u)]               [dx_g ; dhg] = Wg^T da_g     carry += dhg
+ *   dx_t = dx_c + dx_g           da1 = dx_t [W1 o_t + b1 > 0]
+ *   dWg += da_g [x_t ; h_{t-1}]^T   dbg += da_g     dWc += da_c [x_t ; r h_{t-1}]^T   dbc += da_c
+ *   dWm += g_z h_t^T   dbm += g_z   dlogstd += g_l   dW1 += da1 o_t^T   db1 += da1
+ * Supported: state 100; obs_dim 4, 16 or 22; out_dim 1, 2, 4 or 8; hidden1 <= 256; R * T * 24 < 2^31.  Anything else: REX_EINVAL, the
+ * offending field named in rex_last_error.  A step t >= length[r] contributes nothing and is never read.  fp32; every sum in a fixed order:
+ * two calls on the same inputs return the same bits.  The workspace holds the stored activations of every memory slot -- hidden1 rounded up
+ * to 32, + 658 floats per slot: 3 528 bytes at hidden1 = 200 -- the packed weights and the partial gradients. */
+typedef struct RexPpoRnnNet {             /* TORCH layout, as RecurrentGaussianPolicy holds them */
+  int32_t obs_dim, out_dim, hidden1, state;
+  const float *d_w1, *d_b1;               /* [hidden1][obs_dim], [hidden1] */
+  const float *d_wg, *d_bg;               /* [2 state][hidden1 + state], [2 state] */
+  const float *d_wc, *d_bc;               /* [state][hidden1 + state], [state] */
+  const float *d_wm, *d_bm;               /* [out_dim][state], [out_dim] */
+  const float *d_logstd;                  /* [out_dim] */
+} RexPpoRnnNet;
+typedef struct RexPpoRnnGrad {            /* the gradients, shaped like RexPpoRnnNet's tensors */
+  float *d_w1, *d_b1, *d_wg, *d_bg, *d_wc, *d_bc, *d_wm, *d_bm, *d_logstd;
+} RexPpoRnnGrad;
+/* Bytes of workspace rex_ppo_recurrent_policy_loss needs (< 0: unsupported shape, the field named in rex_last_error).  16-byte aligned. */
+REX_API long long rex_ppo_recurrent_workspace_bytes(int rows, int steps, int obs_dim, int out_dim, int hidden1, int state);
+/* d_loss [1] and d_kl_row [R] are always written; grad == NULL makes the call forward-only (the same loss and kl_row, bit for bit).  The
+ * batch is rex_ppo_policy_loss's (d_return unused).  Stateless; launches on `stream`, no host synchronisation. */
+REX_API int rex_ppo_recurrent_policy_loss(const RexPpoRnnNet* net, const RexPpoBatch* batch, const RexPpoRnnGrad* grad, float* d_loss,
+                                          float* d_kl_row, void* d_workspace, void* stream);
+
 REX_API const char* rex_last_error(void);
 REX_API int rex_abi_version(void);
 

@@ -93,6 +93,21 @@ class RexPpoGrad(ctypes.Structure):
                 ("d_w3", ctypes.c_void_p), ("d_b3", ctypes.c_void_p), ("d_logstd", ctypes.c_void_p)]
 
 
+class RexPpoRnnNet(ctypes.Structure):
+    """Mirror of `struct RexPpoRnnNet` (include/rexsim.h): the recurrent policy of the fused recurrent learner, torch layout."""
+    _fields_ = [("obs_dim", ctypes.c_int32), ("out_dim", ctypes.c_int32), ("hidden1", ctypes.c_int32), ("state", ctypes.c_int32),
+                ("d_w1", ctypes.c_void_p), ("d_b1", ctypes.c_void_p), ("d_wg", ctypes.c_void_p), ("d_bg", ctypes.c_void_p),
+                ("d_wc", ctypes.c_void_p), ("d_bc", ctypes.c_void_p), ("d_wm", ctypes.c_void_p), ("d_bm", ctypes.c_void_p),
+                ("d_logstd", ctypes.c_void_p)]
+
+
+class RexPpoRnnGrad(ctypes.Structure):
+    """Mirror of `struct RexPpoRnnGrad` (include/rexsim.h): where the nine gradients go."""
+    _fields_ = [("d_w1", ctypes.c_void_p), ("d_b1", ctypes.c_void_p), ("d_wg", ctypes.c_void_p), ("d_bg", ctypes.c_void_p),
+                ("d_wc", ctypes.c_void_p), ("d_bc", ctypes.c_void_p), ("d_wm", ctypes.c_void_p), ("d_bm", ctypes.c_void_p),
+                ("d_logstd", ctypes.c_void_p)]
+
+
 class RexSimError(RuntimeError):
     pass
 
@@ -154,6 +169,9 @@ _SIGS = {
                              ctypes.c_void_p, ctypes.c_void_p], ctypes.c_int),
     "rex_ppo_value_loss": ([ctypes.POINTER(RexPpoNet), ctypes.POINTER(RexPpoBatch), ctypes.POINTER(RexPpoGrad), ctypes.c_void_p, ctypes.c_void_p,
                             ctypes.c_void_p, ctypes.c_void_p], ctypes.c_int),
+    "rex_ppo_recurrent_workspace_bytes": ([ctypes.c_int] * 6, ctypes.c_longlong),
+    "rex_ppo_recurrent_policy_loss": ([ctypes.POINTER(RexPpoRnnNet), ctypes.POINTER(RexPpoBatch), ctypes.POINTER(RexPpoRnnGrad), ctypes.c_void_p,
+                                       ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p], ctypes.c_int),
     "rex_last_error": ([], ctypes.c_char_p),
     "rex_abi_version": ([], ctypes.c_int),
 }

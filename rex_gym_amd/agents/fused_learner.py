@@ -1,4 +1,4 @@
-"""The fused PPO learner: `PPOConfig(learner="fused")` runs the losses of agents/ppo.py and their parameter gradients in the HIP
+"""The fused PPO learners: `PPOConfig(learner="fused")` runs the losses of agents/ppo.py and their parameter gradients in the HIP
 kernels of csrc/rex_learner.h (rex_ppo_policy_loss, rex_ppo_value_loss, rex_ppo_returns; formulas in include/rexsim.h) instead of
 PyTorch autograd.  Adam, the gradient all-reduce (`PPOAgent._sync`), the filters and the penalty adaptation stay in PyTorch: the kernels
 write the gradients straight into the tensors that ARE the parameters' `.grad`.
@@ -6,6 +6,11 @@ write the gradients straight into the tensors that ARE the parameters' `.grad`.
 Host-only pieces (no GPU needed): `output_seeds`, the hand-derived backward seeds of the policy loss in plain torch -- what the kernel
 computes per sample, checked against autograd in tests/test_fused_learner_host.py -- and `flat_gradients` / `net_struct` / `grad_struct`,
 which lay parameters and gradients out for the C ABI.
+
+`PPOConfig(learner="fused_recurrent")` is the same for the RecurrentGaussianPolicy: its policy loss and the nine gradients by backpropagation
+through time run in the kernels of csrc/rex_learner_rnn.h (rex_ppo_recurrent_policy_loss); the value net is the plain two-layer network and
+stays on rex_ppo_value_loss.  `recurrent_backward` is the host-only restatement of that backward recurrence (tests/
+test_fused_recurrent_learner_host.py holds it to autograd).
 """
 import ctypes
 
@@ -39,6 +44,49 @@ def output_seeds(mean, logstd, old_mean, old_logstd, action, advantage, length, 
     g_mean = (wk * dm * ie2 - ra * dx * ie2) / (R * T)
     g_logstd = (wk * (1 - ev - dm ** 2 * ie2) - ra * (-0.5 + u2)) / (R * T)
     return g_mean, g_logstd, kl_row
+
+
+def recurrent_backward(w1, b1, wg, bg, wc, bc, wm, bm, logstd, observ, old_mean, old_logstd, action, advantage, length, penalty, cutoff, coef):
+    """The policy loss of a RecurrentGaussianPolicy and its nine parameter gradients WITHOUT autograd: the forward recurrence, `output_seeds`,
+    then the backward recurrence of include/rexsim.h in reverse t with carry_T = 0 -- what the kernels of csrc/rex_learner_rnn.h compute.
+    Weights in torch layout (W1 [F, O], Wg [2H, F + H], Wc [H, F + H], Wm [A, H]); observ [R, T, O].  Returns (grads, kl_row) with grads a
+    dict keyed w1, b1, wg, bg, wc, bc, wm, bm, logstd."""
+    R, T, _ = observ.shape
+    F, H = w1.shape[0], wc.shape[0]
+    a1 = observ @ w1.T + b1
+    x = torch.relu(a1)
+    h = torch.zeros((R, H), dtype=observ.dtype, device=observ.device)
+    hp, rs, us, cs, hs = [], [], [], [], []
+    for t in range(T):
+        r, u = torch.sigmoid(torch.cat([x[:, t], h], -1) @ wg.T + bg).chunk(2, -1)
+        c = torch.tanh(torch.cat([x[:, t], r * h], -1) @ wc.T + bc)
+        hp.append(h)
+        h = u * h + (1 - u) * c
+        rs.append(r); us.append(u); cs.append(c); hs.append(h)
+    hs_ = torch.stack(hs, 1)
+    m = torch.tanh(hs_ @ wm.T + bm)
+    g_m, g_l, kl_row = output_seeds(m, logstd.expand_as(m), old_mean, old_logstd, action, advantage, length, penalty, cutoff, coef)
+    g_z = g_m * (1 - m ** 2)
+    grads = {"w1": torch.zeros_like(w1), "b1": torch.zeros_like(b1), "wg": torch.zeros_like(wg), "bg": torch.zeros_like(bg), "wc": torch.zeros_like(wc),
+             "bc": torch.zeros_like(bc), "wm": torch.einsum("rta,rth->ah", g_z, hs_), "bm": g_z.sum((0, 1)), "logstd": g_l.sum((0, 1))}
+    carry = torch.zeros_like(h)
+    for t in range(T - 1, -1, -1):
+        r, u, c, h0 = rs[t], us[t], cs[t], hp[t]
+        dh = g_z[:, t] @ wm + carry
+        du, dc, carry = dh * (h0 - c), dh * (1 - u), dh * u
+        da_c = dc * (1 - c ** 2)
+        dxh = da_c @ wc
+        dx_c, drh = dxh[:, :F], dxh[:, F:]
+        dr = drh * h0
+        carry = carry + drh * r
+        da_g = torch.cat([dr * r * (1 - r), du * u * (1 - u)], -1)
+        dxh = da_g @ wg
+        carry = carry + dxh[:, F:]
+        da1 = (dx_c + dxh[:, :F]) * (a1[:, t] > 0).to(observ.dtype)
+        grads["wg"] += da_g.T @ torch.cat([x[:, t], h0], -1); grads["bg"] += da_g.sum(0)
+        grads["wc"] += da_c.T @ torch.cat([x[:, t], r * h0], -1); grads["bc"] += da_c.sum(0)
+        grads["w1"] += da1.T @ observ[:, t]; grads["b1"] += da1.sum(0)
+    return grads, kl_row
 
 
 def flat_gradients(params):
@@ -89,11 +137,51 @@ def check_config(cfg, device):
     """What PPOConfig(learner="fused") needs; raises ValueError otherwise (PPOAgent.__init__)."""
     if cfg.network != "forward":
         raise ValueError("PPOConfig(learner='fused') is the ForwardGaussianPolicy's learner (network='forward'); the recurrent policy's update is "
-                         "out of its scope and stays on learner='autograd'")
+                         "out of its scope: it runs on learner='fused_recurrent' (or 'autograd')")
     if len(cfg.policy_layers) != 2 or len(cfg.value_layers) != 2:
         raise ValueError("PPOConfig(learner='fused') needs two policy layers and two value layers (the shape of every shipped config)")
     if torch.device(device).type != "cuda":
         raise ValueError("PPOConfig(learner='fused') runs HIP kernels: it needs a CUDA/HIP device, not %r" % (str(device),))
+
+
+def check_config_recurrent(cfg, device):
+    """What PPOConfig(learner="fused_recurrent") needs; raises ValueError otherwise (PPOAgent.__init__)."""
+    if cfg.network != "recurrent":
+        raise ValueError("PPOConfig(learner='fused_recurrent') is the RecurrentGaussianPolicy's learner (network='recurrent'); the forward network "
+                         "runs on learner='fused'")
+    if len(cfg.policy_layers) != 2:
+        raise ValueError("PPOConfig(learner='fused_recurrent') needs two policy layers: one Linear layer in front of the GRU cell")
+    if len(cfg.value_layers) != 2:
+        raise ValueError("PPOConfig(learner='fused_recurrent') needs two value layers (the shape of every shipped config)")
+    if torch.device(device).type != "cuda":
+        raise ValueError("PPOConfig(learner='fused_recurrent') runs HIP kernels: it needs a CUDA/HIP device, not %r" % (str(device),))
+
+
+RNN_FIELDS = ("d_w1", "d_b1", "d_wm", "d_bm", "d_logstd", "d_wg", "d_bg", "d_wc", "d_bc")     # the order of RecurrentGaussianPolicy.policy_parameters()
+
+
+def rnn_net_struct(params):
+    """RexPpoRnnNet of a RecurrentGaussianPolicy's policy_parameters(): W1, b1, Wm, bm, logstd, Wg, bg, Wc, bc, torch layout as they are."""
+    params = list(params)
+    if len(params) != 9:
+        raise ValueError("a recurrent policy has nine tensors: W1, b1, Wm, bm, logstd, Wg, bg, Wc, bc")
+    w1, wm, wg, wc = params[0], params[2], params[5], params[7]
+    F, H = w1.shape[0], wc.shape[0]
+    if wg.shape != (2 * H, F + H) or wc.shape != (H, F + H) or wm.shape[1] != H:
+        raise ValueError("the tensors are not a Linear layer, a GRU cell and a mean layer")
+    s = _lib.RexPpoRnnNet()
+    for n, t in zip(RNN_FIELDS, params):
+        setattr(s, n, t.data_ptr())
+    s.hidden1, s.obs_dim = w1.shape
+    s.out_dim, s.state = wm.shape
+    return s
+
+
+def rnn_grad_struct(views):
+    s = _lib.RexPpoRnnGrad()
+    for n, t in zip(RNN_FIELDS, list(views)):
+        setattr(s, n, t.data_ptr())
+    return s
 
 
 class FusedLearner:
@@ -178,3 +266,38 @@ class FusedLearner:
         out = torch.empty((self.rows, self.steps), device=self.device)
         self.value_loss(observ, torch.zeros_like(out), grad=False, value_out=out)     # (the return block only feeds the loss, which is dropped)
         return out
+
+
+class FusedRecurrentLearner(FusedLearner):
+    """The same for a RecurrentGaussianPolicy: the policy loss runs on rex_ppo_recurrent_policy_loss (its own workspace: the stored activations
+    of every memory slot), the value net and the return scans on FusedLearner's calls."""
+
+    def __init__(self, net, rows, steps, device):
+        self.device = torch.device(device)
+        self.rows, self.steps = int(rows), int(steps)
+        self.policy_params, self.value_params = net.policy_parameters(), net.value_parameters()
+        self.policy_flat, self.policy_grads = flat_gradients(self.policy_params)
+        self.value_flat, self.value_grads = flat_gradients(self.value_params)
+        self._L = _lib.lib()
+        n, v = rnn_net_struct(self.policy_params), net_struct(self.value_params)
+        need = [self._L.rex_ppo_recurrent_workspace_bytes(self.rows, self.steps, n.obs_dim, n.out_dim, n.hidden1, n.state)]
+        if need[0] >= 0:
+            need.append(self._L.rex_ppo_workspace_bytes(self.rows, self.steps, v.obs_dim, v.out_dim, v.hidden1, v.hidden2))
+        if need[-1] < 0:
+            raise ValueError("the fused recurrent learner does not offer this shape: " + self._L.rex_last_error().decode("utf-8", "replace"))
+        self.policy_workspace = torch.empty(need[0] // 4, dtype=torch.float32, device=self.device)
+        self.workspace = torch.empty(need[1] // 4, dtype=torch.float32, device=self.device)
+        self.length = torch.zeros(self.rows, dtype=torch.int32, device=self.device)
+        self.kl_row = torch.zeros(self.rows, device=self.device)
+        self._scratch_loss = torch.zeros(1, device=self.device)
+
+    def policy_loss(self, observ, action, old_mean, old_logstd, advantage, penalty, cutoff, coef, loss_out=None, grad=True):
+        b, keep = self._batch(observ, action=action, old_mean=old_mean, old_logstd=old_logstd, advantage=advantage)
+        b.penalty, b.kl_cutoff, b.kl_cutoff_coef = float(penalty), float(cutoff), float(coef)
+        loss_out = self._scratch_loss if loss_out is None else loss_out
+        net, g = rnn_net_struct(self.policy_params), rnn_grad_struct(self.policy_grads)
+        with torch.cuda.device(self.device):
+            _lib.check(self._L.rex_ppo_recurrent_policy_loss(ctypes.byref(net), ctypes.byref(b), ctypes.byref(g) if grad else None, loss_out.data_ptr(),
+                                                             self.kl_row.data_ptr(), self.policy_workspace.data_ptr(), self._stream()),
+                       "rex_ppo_recurrent_policy_loss")
+        return loss_out, self.kl_row

@@ -1,6 +1,7 @@
 """KL-penalty PPO of the reference (rex_gym/agents/ppo/algorithm.py, a TF1 graph) restated in PyTorch on the device.
 The update's losses and gradients run through PyTorch autograd (PPOConfig.learner = "autograd", the default) or, for the forward
-network, through the fused HIP kernels of csrc/rex_learner.h (learner = "fused", agents/fused_learner.py).
+network, through the fused HIP kernels of csrc/rex_learner.h (learner = "fused", agents/fused_learner.py); for the recurrent network,
+through those of csrc/rex_learner_rnn.h (learner = "fused_recurrent").
 
 The reference learner pulls numpy arrays out of N environment processes every step; here observations, rewards and
 done flags are the device tensors RexBatchEnv returns, the episode buffers live in HBM and nothing crosses PCIe.
@@ -46,7 +47,8 @@ class PPOConfig:
     max_length: int = 2000
     network: str = "forward"        # "forward": ForwardGaussianPolicy (every shipped config); "recurrent": RecurrentGaussianPolicy
     learner: str = "autograd"       # "autograd": the losses below through PyTorch autograd; "fused": the HIP kernels of csrc/rex_learner.h
-                                    # (agents/fused_learner.py: forward network, two + two layers, a HIP device)
+                                    # (agents/fused_learner.py: forward network, two + two layers, a HIP device); "fused_recurrent": the same for
+                                    # network = "recurrent" (csrc/rex_learner_rnn.h: one Linear layer in front of the GRU cell)
 
 
 class StreamingNormalize:
@@ -259,11 +261,14 @@ class PPOAgent:
     def __init__(self, num_agents, obs_dim, action_dim, cfg=None, device="cuda", seed=0, sync_gradients=False):
         self.cfg = cfg = cfg or PPOConfig()
         self.n, self.device = num_agents, torch.device(device)
-        if cfg.learner not in ("autograd", "fused"):
-            raise ValueError("PPOConfig.learner must be 'autograd' or 'fused'")
+        if cfg.learner not in ("autograd", "fused", "fused_recurrent"):
+            raise ValueError("PPOConfig.learner must be 'autograd', 'fused' or 'fused_recurrent'")
         if cfg.learner == "fused":
             from .fused_learner import check_config
             check_config(cfg, self.device)
+        if cfg.learner == "fused_recurrent":
+            from .fused_learner import check_config_recurrent
+            check_config_recurrent(cfg, self.device)
         gen = torch.Generator(device="cpu"); gen.manual_seed(seed)
         with torch.random.fork_rng(devices=[]):
             torch.manual_seed(seed)
@@ -290,6 +295,9 @@ class PPOAgent:
         if cfg.learner == "fused":
             from .fused_learner import FusedLearner
             self._fused = FusedLearner(self.net, cfg.update_every, T, self.device)
+        if cfg.learner == "fused_recurrent":
+            from .fused_learner import FusedRecurrentLearner
+            self._fused = FusedRecurrentLearner(self.net, cfg.update_every, T, self.device)
         self._full_episodes_unpolled, self._warned_unpolled = 0, False
         self.last = None
         self.updates = 0
@@ -411,7 +419,7 @@ class PPOAgent:
             losses.append(loss.detach())
         return {"value_loss": float(torch.stack(losses).mean())}
 
-    # ---- the same three steps on the fused learner (cfg.learner == "fused"): the kernels compute what the autograd lines compute ----
+    # ---- the same three steps on the fused learner (cfg.learner == "fused" or "fused_recurrent"): the kernels compute what the autograd lines compute ----
     @torch.no_grad()
     def _update_value_fused(self, observ, reward, length):
         fl = self._fused
@@ -650,8 +658,9 @@ if __name__ == "__main__":   # python -m rex_gym_amd.agents.ppo --task walk --en
     ap.add_argument("--segment", type=int, default=25)
     ap.add_argument("--network", default="forward", choices=["forward", "recurrent"],
                     help="forward: ForwardGaussianPolicy (every shipped config); recurrent: RecurrentGaussianPolicy, a GRU cell as the last policy layer")
-    ap.add_argument("--learner", default="autograd", choices=["autograd", "fused"],
-                    help="autograd: the update through PyTorch autograd; fused: the HIP loss / gradient kernels (agents/fused_learner.py; forward network only)")
+    ap.add_argument("--learner", default="autograd", choices=["autograd", "fused", "fused_recurrent"],
+                    help="autograd: the update through PyTorch autograd; fused: the HIP loss / gradient kernels (agents/fused_learner.py; forward network "
+                         "only); fused_recurrent: the same for --network recurrent")
     ap.add_argument("--toe-friction", type=float, default=None, help="pin the toe friction (RexBatchEnv(friction_range=(f, f))); the standup task matches its "
                                                                      "PyBullet record at 0.25 (DESIGN.md section 2)")
     ap.add_argument("--logdir", default=None, help="write the trained policy there as a TensorFlow-1 checkpoint the reference's policy player "

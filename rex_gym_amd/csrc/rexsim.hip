@@ -7,6 +7,7 @@
 #include "rex_render.h"
 #include "rex_visual_gen.h"
 #include "rex_learner.h"
+#include "rex_learner_rnn.h"
 #include <algorithm>
 #include <cstdarg>
 #include <cstring>
@@ -1329,6 +1330,96 @@ int rex_ppo_policy_loss(const RexPpoNet* net, const RexPpoBatch* batch, const Re
 
 int rex_ppo_value_loss(const RexPpoNet* net, const RexPpoBatch* batch, const RexPpoGrad* grad, float* d_loss, float* d_value_out, void* d_workspace, void* stream) {
   return ppo_loss("rex_ppo_value_loss", true, net, batch, grad, d_loss, nullptr, d_value_out, d_workspace, (hipStream_t)stream);
+}
+
+// ---- the fused recurrent PPO learner (rex_learner_rnn.h) ----
+static int rnn_check(const char* who, int rows, int steps, int obs_dim, int out_dim, int hidden1, int state) {
+  if (state != REX_RNN_H) return failf(REX_EINVAL, "%s: state %d is not offered (the GRU cell has %d units)", who, state, REX_RNN_H);
+  if (obs_dim != 4 && obs_dim != 16 && obs_dim != 22) return failf(REX_EINVAL, "%s: obs_dim %d is not offered (4, 16 or 22)", who, obs_dim);
+  if (out_dim != 1 && out_dim != 2 && out_dim != 4 && out_dim != 8) return failf(REX_EINVAL, "%s: out_dim %d is not offered (action_dim 1, 2, 4 or 8)", who, out_dim);
+  if (hidden1 < 1 || hidden1 > REX_PPO_MAX_H1) return failf(REX_EINVAL, "%s: hidden1 %d is not offered (1..%d)", who, hidden1, REX_PPO_MAX_H1);
+  if (rows < 1 || steps < 1 || (long long)rows * steps * 24 >= (1ll << 31))
+    return failf(REX_EINVAL, "%s: a memory of %d rows x %d steps is not offered (rows, steps >= 1, rows * steps * 24 < 2^31)", who, rows, steps);
+  return REX_OK;
+}
+
+long long rex_ppo_recurrent_workspace_bytes(int rows, int steps, int obs_dim, int out_dim, int hidden1, int state) {
+  if (rnn_check("rex_ppo_recurrent_workspace_bytes", rows, steps, obs_dim, out_dim, hidden1, state) != REX_OK) return REX_EINVAL;
+  return (long long)(sizeof(float) * rex::rnn_workspace(rows, steps, obs_dim, hidden1).total);
+}
+
+int rex_ppo_recurrent_policy_loss(const RexPpoRnnNet* net, const RexPpoBatch* b, const RexPpoRnnGrad* grad, float* d_loss, float* d_kl_row, void* d_workspace,
+                                  void* stream) {
+  const char* who = "rex_ppo_recurrent_policy_loss";
+  if (!net || !b) return failf(REX_EINVAL, "%s: null pointer", who);
+  const int rc = rnn_check(who, b->rows, b->steps, net->obs_dim, net->out_dim, net->hidden1, net->state);
+  if (rc != REX_OK) return rc;
+  if (!net->d_w1 || !net->d_b1 || !net->d_wg || !net->d_bg || !net->d_wc || !net->d_bc || !net->d_wm || !net->d_bm || !net->d_logstd)
+    return failf(REX_EINVAL, "%s: null weight pointer", who);
+  if (!b->d_observ || !b->d_length || !b->d_action || !b->d_old_mean || !b->d_old_logstd || !b->d_advantage) return failf(REX_EINVAL, "%s: null memory block", who);
+  if (!d_loss || !d_kl_row || !d_workspace) return failf(REX_EINVAL, "%s: null output or workspace pointer", who);
+  if (grad && (!grad->d_w1 || !grad->d_b1 || !grad->d_wg || !grad->d_bg || !grad->d_wc || !grad->d_bc || !grad->d_wm || !grad->d_bm || !grad->d_logstd))
+    return failf(REX_EINVAL, "%s: null gradient pointer (pass grad = NULL for a forward-only call)", who);
+  hipStream_t st = (hipStream_t)stream;
+  const int O = net->obs_dim, A = net->out_dim, F = net->hidden1, R = b->rows, T = b->steps, H = REX_RNN_H;
+  const rex::RnnWs ws = rex::rnn_workspace(R, T, O, F);
+  float* w = static_cast<float*>(d_workspace);
+  rex::RnnArgs a{};
+  a.w1 = net->d_w1; a.b1 = net->d_b1; a.wg = net->d_wg; a.bg = net->d_bg; a.wc = net->d_wc; a.bc = net->d_bc; a.wm = net->d_wm; a.bm = net->d_bm; a.logstd = net->d_logstd;
+  a.observ = b->d_observ; a.action = b->d_action; a.old_mean = b->d_old_mean; a.old_logstd = b->d_old_logstd; a.advantage = b->d_advantage; a.length = b->d_length;
+  a.wht = w + ws.wht; a.wh = w + ws.wh; a.wxp = w + ws.wxp; a.wxt = w + ws.wxt; a.biasp = w + ws.biasp; a.x = w + ws.x; a.act = w + ws.act; a.hs = w + ws.hs;
+  a.rh = w + ws.rh; a.gzl = w + ws.gzl; a.klt = w + ws.klt; a.sat = w + ws.sat; a.rowloss = w + ws.rowloss; a.pw = w + ws.pw; a.pb = w + ws.pb; a.pm = w + ws.pm;
+  a.pz = w + ws.pz; a.p1 = w + ws.p1; a.kl_row = d_kl_row;
+  a.O = O; a.A = A; a.F = F; a.Fp = ws.Fp; a.R = R; a.T = T; a.NT = ws.ntiles; a.ksplit = ws.ksplit; a.osplit = ws.osplit;
+  a.penalty = b->penalty; a.cutoff = b->kl_cutoff; a.coef = b->kl_cutoff_coef;
+  a.inv_rt = (float)(1.0 / ((double)R * (double)T));
+  const size_t N = (size_t)R * T;
+  const int tiles = R * ws.ntiles, scan_groups = (R + REX_RNN_ROWS - 1) / REX_RNN_ROWS;
+  const size_t lds = sizeof(float) * (size_t)rex::rnn_scan_lds_floats();     // more than 64 KB of dynamic LDS: the functions' limit is raised
+  const unsigned slots = (unsigned)((N + 255) / 256);
+  hipLaunchKernelGGL(rex::rex_rnn_pack_kernel, dim3((std::max(REX_RNN_GP * ws.Fp, 3 * H * H) + 255) / 256), dim3(256), 0, st, a);
+  HIPCHK(hipGetLastError());
+  hipLaunchKernelGGL(rex::rex_rnn_input_kernel, dim3((unsigned)((N * ws.Fp + 255) / 256)), dim3(256), 0, st, a);
+  HIPCHK(hipGetLastError());
+  hipLaunchKernelGGL(rex::rex_rnn_rows_kernel<false>, dim3(tiles), dim3(256), 0, st, a);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&rex::rex_rnn_scan_fwd_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  hipLaunchKernelGGL(rex::rex_rnn_scan_fwd_kernel, dim3(scan_groups), dim3(REX_RNN_SCAN_THREADS), lds, st, a);
+  HIPCHK(hipGetLastError());
+  hipLaunchKernelGGL(rex::rex_rnn_head_kernel<false>, dim3(slots), dim3(256), 0, st, a);
+  HIPCHK(hipGetLastError());
+  hipLaunchKernelGGL(rex::rex_rnn_rowsum_kernel, dim3(R), dim3(256), 0, st, a, d_kl_row);
+  HIPCHK(hipGetLastError());
+  hipLaunchKernelGGL(rex::rex_rnn_loss_kernel, dim3(1), dim3(256), 0, st, a, d_loss);
+  HIPCHK(hipGetLastError());
+  if (!grad) return REX_OK;
+  hipLaunchKernelGGL(rex::rex_rnn_head_kernel<true>, dim3(slots), dim3(256), 0, st, a);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&rex::rex_rnn_scan_bwd_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  hipLaunchKernelGGL(rex::rex_rnn_scan_bwd_kernel, dim3(scan_groups), dim3(REX_RNN_SCAN_THREADS), lds, st, a);
+  HIPCHK(hipGetLastError());
+  const int NI = (ws.Fp + REX_RNN_HP) / 32;
+  hipLaunchKernelGGL(rex::rex_rnn_wgrad_kernel, dim3((6 * NI + 3) / 4, ws.ksplit), dim3(256), 0, st, a);
+  HIPCHK(hipGetLastError());
+  hipLaunchKernelGGL(rex::rex_rnn_outer_kernel<0>, dim3(REX_RNN_GP / 128, ws.osplit), dim3(128), 0, st, a, (const float*)nullptr, 0, (const float*)a.act, REX_RNN_GP,
+                     REX_RNN_GP, a.pb);
+  HIPCHK(hipGetLastError());
+  hipLaunchKernelGGL(rex::rex_rnn_outer_kernel<8>, dim3(1, ws.osplit), dim3(128), 0, st, a, (const float*)a.gzl, 16, (const float*)a.hs, REX_RNN_HP, H, a.pm);
+  HIPCHK(hipGetLastError());
+  hipLaunchKernelGGL(rex::rex_rnn_outer_kernel<0>, dim3(1, ws.osplit), dim3(128), 0, st, a, (const float*)nullptr, 0, (const float*)a.gzl, 16, 16, a.pz);
+  HIPCHK(hipGetLastError());
+  hipLaunchKernelGGL(rex::rex_rnn_rows_kernel<true>, dim3(tiles), dim3(256), 0, st, a);      // X <- da1 (the weight-gradient product has read X)
+  HIPCHK(hipGetLastError());
+  const dim3 g1((ws.Fp + 127) / 128, ws.osplit);
+  if (O == 4) hipLaunchKernelGGL(rex::rex_rnn_outer_kernel<4>, g1, dim3(128), 0, st, a, a.observ, O, (const float*)a.x, ws.Fp, ws.Fp, a.p1);
+  else if (O == 16) hipLaunchKernelGGL(rex::rex_rnn_outer_kernel<16>, g1, dim3(128), 0, st, a, a.observ, O, (const float*)a.x, ws.Fp, ws.Fp, a.p1);
+  else hipLaunchKernelGGL(rex::rex_rnn_outer_kernel<22>, g1, dim3(128), 0, st, a, a.observ, O, (const float*)a.x, ws.Fp, ws.Fp, a.p1);
+  HIPCHK(hipGetLastError());
+  const int np = F * O + F + 3 * H * (F + H) + 3 * H + A * H + 2 * A;
+  const rex::RnnGradDev g{grad->d_w1, grad->d_b1, grad->d_wg, grad->d_bg, grad->d_wc, grad->d_bc, grad->d_wm, grad->d_bm, grad->d_logstd};
+  hipLaunchKernelGGL(rex::rex_rnn_final_kernel, dim3((np + 255) / 256), dim3(256), 0, st, a, g);
+  HIPCHK(hipGetLastError());
+  return REX_OK;
 }
 
 #ifdef REX_PROF   /* developer build only (tools/prof_sections.py): cycle counters of the sections of a substep */

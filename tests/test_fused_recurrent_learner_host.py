@@ -1,0 +1,82 @@
+"""The host side of the fused recurrent PPO learner (agents/fused_learner.py, include/rexsim.h): the ABI surface, the config checks and the
+hand-derived backward recurrence against fp64 autograd of agents/ppo.py's own classes.  CPU only."""
+import os
+import re
+
+import pytest
+import torch
+
+from rex_gym_amd.agents import PPOAgent, PPOConfig
+
+import fused_recurrent_cases as rc
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+ENTRY_POINTS = ("rex_ppo_recurrent_workspace_bytes", "rex_ppo_recurrent_policy_loss")
+
+
+@pytest.mark.parametrize("shape", ["r5", "r67"])
+def test_backward_recurrence_matches_fp64_autograd(shape):
+    """The nine gradient tensors and kl_row of `_update_policy`'s loss through the GRU: recurrent_backward (no autograd) against fp64 autograd
+    of RecurrentGaussianPolicy, max|diff| / max|ref| <= 1e-12 per tensor; rows on both sides of the KL cutoff, so the w_r term is tested."""
+    from rex_gym_amd.agents.fused_learner import recurrent_backward
+    c = rc.to(rc.make_case(shape, 4, 2), "cpu", torch.float64)
+    want = rc.autograd(c, "cpu", torch.float64)
+    kl = want["kl_row"]
+    above, below = int((kl > rc.CUTOFF).sum()), int((kl <= rc.CUTOFF).sum())
+    print("%s: %d rows above the cutoff, %d at or below" % (shape, above, below))
+    assert above >= 1 and below >= 1, kl
+    p = dict(zip(rc.NAMES, [q.detach() for q in c["net"].policy_parameters()]))
+    grads, kl_row = recurrent_backward(p["w1"], p["b1"], p["wg"], p["bg"], p["wc"], p["bc"], p["wm"], p["bm"], p["logstd"], c["observ"], c["old_mean"],
+                                       c["old_logstd"], c["action"], c["advantage"], c["length"], rc.PENALTY, rc.CUTOFF, rc.COEF)
+    for name, ref in list(zip(rc.NAMES, want["policy_grads"])) + [("kl_row", kl)]:
+        got = kl_row if name == "kl_row" else grads[name]
+        err = float((got - ref).abs().max() / ref.abs().max())
+        print("%s %s: %.3e" % (shape, name, err))
+        assert got.shape == ref.shape and err <= 1e-12, (name, err)
+
+
+def test_the_abi_declares_binds_and_exports_the_recurrent_learner():
+    from rex_gym_amd import _lib
+    hdr = open(os.path.join(ROOT, "include", "rexsim.h")).read()
+    declared = set(re.findall(r"REX_API\s+[\w\s\*]+?\b(rex_\w+)\s*\(", hdr))
+    assert set(ENTRY_POINTS) <= declared and set(ENTRY_POINTS) <= set(_lib.EXPORTED_SYMBOLS)
+    assert re.search(r"\}\s*RexPpoRnnNet\s*;", hdr) and re.search(r"\}\s*RexPpoRnnGrad\s*;", hdr)
+    assert re.search(r"#define\s+REX_ABI_VERSION\s+6\b", hdr) and _lib.ABI_VERSION == 6
+    lib = _lib.lib()
+    for name in ENTRY_POINTS:
+        assert hasattr(lib, name)
+    assert lib.rex_abi_version() == 6
+    assert lib.rex_ppo_recurrent_workspace_bytes(4096, 400, 4, 2, 200, 100) > 0
+    assert lib.rex_ppo_recurrent_workspace_bytes(25, 2000, 22, 8, 256, 100) > 0
+    assert lib.rex_ppo_recurrent_workspace_bytes(25, 2000, 4, 2, 200, 64) == -1 and b"state 64" in lib.rex_last_error()
+    assert lib.rex_ppo_recurrent_workspace_bytes(25, 2000, 5, 2, 200, 100) == -1 and b"obs_dim 5" in lib.rex_last_error()
+
+
+def test_the_struct_fields_follow_policy_parameters():
+    from rex_gym_amd.agents import ppo
+    from rex_gym_amd.agents.fused_learner import flat_gradients, rnn_grad_struct, rnn_net_struct
+    net = ppo.RecurrentGaussianPolicy(16, 4, PPOConfig(network="recurrent"))
+    params = net.policy_parameters()
+    n = rnn_net_struct(params)
+    assert (n.obs_dim, n.out_dim, n.hidden1, n.state) == (16, 4, 200, 100)
+    assert n.d_w1 == net.policy[0].weight.data_ptr() and n.d_wg == net.gates.weight.data_ptr() and n.d_bc == net.candidate.bias.data_ptr()
+    assert n.d_wm == net.mean.weight.data_ptr() and n.d_logstd == net.logstd.data_ptr()
+    _, views = flat_gradients(params)
+    g = rnn_grad_struct(views)
+    assert g.d_wc == net.candidate.weight.grad.data_ptr() and g.d_bm == net.mean.bias.grad.data_ptr()
+    with pytest.raises(ValueError):
+        rnn_net_struct(params[:7])
+
+
+def test_fused_recurrent_states_what_it_needs():
+    assert PPOConfig().learner == "autograd"
+    with pytest.raises(ValueError, match="fused_recurrent"):         # the forward learner names the recurrent one
+        PPOAgent(4, 4, 2, PPOConfig(learner="fused", network="recurrent"), device="cuda")
+    with pytest.raises(ValueError, match="network='recurrent'"):
+        PPOAgent(4, 4, 2, PPOConfig(learner="fused_recurrent"), device="cuda")
+    with pytest.raises(ValueError, match="two policy layers"):
+        PPOAgent(4, 4, 2, PPOConfig(learner="fused_recurrent", network="recurrent", policy_layers=(200, 100, 100)), device="cuda")
+    with pytest.raises(ValueError, match="two value layers"):
+        PPOAgent(4, 4, 2, PPOConfig(learner="fused_recurrent", network="recurrent", value_layers=(32,)), device="cuda")
+    with pytest.raises(ValueError, match="device"):
+        PPOAgent(4, 4, 2, PPOConfig(learner="fused_recurrent", network="recurrent"), device="cpu")
