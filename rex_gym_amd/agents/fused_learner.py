@@ -1,16 +1,18 @@
 """The fused PPO learners: `PPOConfig(learner="fused")` runs the losses of agents/ppo.py and their parameter gradients in the HIP
-kernels of csrc/rex_learner.h (rex_ppo_policy_loss, rex_ppo_value_loss, rex_ppo_returns; formulas in include/rexsim.h) instead of
-PyTorch autograd.  Adam, the gradient all-reduce (`PPOAgent._sync`), the filters and the penalty adaptation stay in PyTorch: the kernels
-write the gradients straight into the tensors that ARE the parameters' `.grad`.
-
-Host-only pieces (no GPU needed): `output_seeds`, the hand-derived backward seeds of the policy loss in plain torch -- what the kernel
-computes per sample, checked against autograd in tests/test_fused_learner_host.py -- and `flat_gradients` / `net_struct` / `grad_struct`,
-which lay parameters and gradients out for the C ABI.
+kernels of csrc/rex_learner.h (rex_ppo_policy_loss, rex_ppo_value_loss, rex_ppo_returns; entry points in csrc/rex_learner.hip, formulas in
+include/rexsim.h) instead of PyTorch autograd.  Adam, the gradient all-reduce (`PPOAgent._sync`), the filters and the penalty adaptation
+stay in PyTorch: the kernels write the gradients straight into the tensors that ARE the parameters' `.grad`.
 
 `PPOConfig(learner="fused_recurrent")` is the same for the RecurrentGaussianPolicy: its policy loss and the nine gradients by backpropagation
 through time run in the kernels of csrc/rex_learner_rnn.h (rex_ppo_recurrent_policy_loss); the value net is the plain two-layer network and
-stays on rex_ppo_value_loss.  `recurrent_backward` is the host-only restatement of that backward recurrence (tests/
-test_fused_recurrent_learner_host.py holds it to autograd).
+stays on rex_ppo_value_loss.  One class does the work: `FusedLearner` holds the buffers, the workspace sizing and the calls;
+`FusedRecurrentLearner` only overrides what differs -- its struct builders, its workspace-size call, its entry point and that the policy keeps
+a workspace of its own.  `check_config(cfg, device, learner)` states what either needs.
+
+Host-only pieces (no GPU needed): `output_seeds`, the hand-derived backward seeds of the policy loss in plain torch -- what the kernels
+compute per sample, checked against autograd in tests/test_fused_learner_host.py; `recurrent_backward`, the restatement of the backward
+recurrence (tests/test_fused_recurrent_learner_host.py holds it to autograd); and `flat_gradients` / `net_struct` / `grad_struct` /
+`rnn_net_struct` / `rnn_grad_struct`, which lay parameters and gradients out for the C ABI (one filler, `_pointer_struct`, behind the four).
 """
 import ctypes
 
@@ -105,21 +107,33 @@ def flat_gradients(params):
     return flat, views
 
 
-def _tensors_struct(cls, tensors):
-    """w1, b1, w2, b2, w3, b3 (and logstd) -> the d_* pointer fields of a RexPpoNet / RexPpoGrad"""
-    names = ("d_w1", "d_b1", "d_w2", "d_b2", "d_w3", "d_b3", "d_logstd")
-    if len(tensors) not in (6, 7):
-        raise ValueError("a two-layer network has six tensors (and logstd): W1, b1, W2, b2, W3, b3")
+FORWARD_FIELDS = ("d_w1", "d_b1", "d_w2", "d_b2", "d_w3", "d_b3", "d_logstd")                 # a two-layer net's parameters (the value net: no logstd)
+RNN_FIELDS = ("d_w1", "d_b1", "d_wm", "d_bm", "d_logstd", "d_wg", "d_bg", "d_wc", "d_bc")     # the order of RecurrentGaussianPolicy.policy_parameters()
+
+
+def _pointer_struct(cls, fields, tensors, counts, what):
+    """The d_* pointer fields of a RexPpo*Net / RexPpo*Grad from tensors in the order of `fields`; `counts`: how many there may be."""
+    tensors = list(tensors)
+    if len(tensors) not in counts:
+        raise ValueError(what)
     s = cls()
-    for n, t in zip(names, tensors):
+    for n, t in zip(fields, tensors):
         setattr(s, n, t.data_ptr())
     return s
+
+
+def _forward_struct(cls, tensors):
+    return _pointer_struct(cls, FORWARD_FIELDS, tensors, (6, 7), "a two-layer network has six tensors (and logstd): W1, b1, W2, b2, W3, b3")
+
+
+def _rnn_struct(cls, tensors):
+    return _pointer_struct(cls, RNN_FIELDS, tensors, (9,), "a recurrent policy has nine tensors: W1, b1, Wm, bm, logstd, Wg, bg, Wc, bc")
 
 
 def net_struct(params):
     """RexPpoNet of a network given as its tensors in torch order and layout: Linear weights [out][in] as they are."""
     params = list(params)
-    s = _tensors_struct(_lib.RexPpoNet, params)
+    s = _forward_struct(_lib.RexPpoNet, params)
     w1, w2, w3 = params[0], params[2], params[4]
     if w2.shape[1] != w1.shape[0] or w3.shape[1] != w2.shape[0] or any(params[2 * k + 1].shape != (params[2 * k].shape[0],) for k in range(3)):
         raise ValueError("the tensors are not a chain of three Linear layers")
@@ -130,63 +144,55 @@ def net_struct(params):
 
 
 def grad_struct(views):
-    return _tensors_struct(_lib.RexPpoGrad, list(views))
-
-
-def check_config(cfg, device):
-    """What PPOConfig(learner="fused") needs; raises ValueError otherwise (PPOAgent.__init__)."""
-    if cfg.network != "forward":
-        raise ValueError("PPOConfig(learner='fused') is the ForwardGaussianPolicy's learner (network='forward'); the recurrent policy's update is "
-                         "out of its scope: it runs on learner='fused_recurrent' (or 'autograd')")
-    if len(cfg.policy_layers) != 2 or len(cfg.value_layers) != 2:
-        raise ValueError("PPOConfig(learner='fused') needs two policy layers and two value layers (the shape of every shipped config)")
-    if torch.device(device).type != "cuda":
-        raise ValueError("PPOConfig(learner='fused') runs HIP kernels: it needs a CUDA/HIP device, not %r" % (str(device),))
-
-
-def check_config_recurrent(cfg, device):
-    """What PPOConfig(learner="fused_recurrent") needs; raises ValueError otherwise (PPOAgent.__init__)."""
-    if cfg.network != "recurrent":
-        raise ValueError("PPOConfig(learner='fused_recurrent') is the RecurrentGaussianPolicy's learner (network='recurrent'); the forward network "
-                         "runs on learner='fused'")
-    if len(cfg.policy_layers) != 2:
-        raise ValueError("PPOConfig(learner='fused_recurrent') needs two policy layers: one Linear layer in front of the GRU cell")
-    if len(cfg.value_layers) != 2:
-        raise ValueError("PPOConfig(learner='fused_recurrent') needs two value layers (the shape of every shipped config)")
-    if torch.device(device).type != "cuda":
-        raise ValueError("PPOConfig(learner='fused_recurrent') runs HIP kernels: it needs a CUDA/HIP device, not %r" % (str(device),))
-
-
-RNN_FIELDS = ("d_w1", "d_b1", "d_wm", "d_bm", "d_logstd", "d_wg", "d_bg", "d_wc", "d_bc")     # the order of RecurrentGaussianPolicy.policy_parameters()
+    return _forward_struct(_lib.RexPpoGrad, views)
 
 
 def rnn_net_struct(params):
     """RexPpoRnnNet of a RecurrentGaussianPolicy's policy_parameters(): W1, b1, Wm, bm, logstd, Wg, bg, Wc, bc, torch layout as they are."""
     params = list(params)
-    if len(params) != 9:
-        raise ValueError("a recurrent policy has nine tensors: W1, b1, Wm, bm, logstd, Wg, bg, Wc, bc")
+    s = _rnn_struct(_lib.RexPpoRnnNet, params)
     w1, wm, wg, wc = params[0], params[2], params[5], params[7]
     F, H = w1.shape[0], wc.shape[0]
     if wg.shape != (2 * H, F + H) or wc.shape != (H, F + H) or wm.shape[1] != H:
         raise ValueError("the tensors are not a Linear layer, a GRU cell and a mean layer")
-    s = _lib.RexPpoRnnNet()
-    for n, t in zip(RNN_FIELDS, params):
-        setattr(s, n, t.data_ptr())
     s.hidden1, s.obs_dim = w1.shape
     s.out_dim, s.state = wm.shape
     return s
 
 
 def rnn_grad_struct(views):
-    s = _lib.RexPpoRnnGrad()
-    for n, t in zip(RNN_FIELDS, list(views)):
-        setattr(s, n, t.data_ptr())
-    return s
+    return _rnn_struct(_lib.RexPpoRnnGrad, views)
+
+
+# learner -> its network, what it says of another one, and its (layer settings, what it says unless each has two entries)
+_CONFIG_NEEDS = {
+    "fused": ("forward", "is the ForwardGaussianPolicy's learner (network='forward'); the recurrent policy's update is out of its scope: it runs on "
+                         "learner='fused_recurrent' (or 'autograd')",
+              [(("policy_layers", "value_layers"), "needs two policy layers and two value layers (the shape of every shipped config)")]),
+    "fused_recurrent": ("recurrent", "is the RecurrentGaussianPolicy's learner (network='recurrent'); the forward network runs on learner='fused'",
+                        [(("policy_layers",), "needs two policy layers: one Linear layer in front of the GRU cell"),
+                         (("value_layers",), "needs two value layers (the shape of every shipped config)")]),
+}
+
+
+def check_config(cfg, device, learner):
+    """What PPOConfig(learner="fused" / "fused_recurrent") needs; raises ValueError otherwise (PPOAgent.__init__)."""
+    network, other_network, layers = _CONFIG_NEEDS[learner]
+    who = "PPOConfig(learner=%r) " % learner
+    if cfg.network != network:
+        raise ValueError(who + other_network)
+    for fields, message in layers:
+        if any(len(getattr(cfg, f)) != 2 for f in fields):
+            raise ValueError(who + message)
+    if torch.device(device).type != "cuda":
+        raise ValueError(who + "runs HIP kernels: it needs a CUDA/HIP device, not %r" % (str(device),))
 
 
 class FusedLearner:
-    """The kernels behind a PPOAgent: owns the flat gradient buffers (every parameter's .grad is a view into them), the workspace and the
-    int32 copy of the memory's lengths.  Every call launches on the current stream and does not synchronise with the host."""
+    """The kernels behind a PPOAgent: owns the flat gradient buffers (every parameter's .grad is a view into them), the workspaces and the
+    int32 copy of the memory's lengths.  Every call launches on the current stream and does not synchronise with the host.  A subclass for
+    another policy network overrides the four `_policy_*` methods and, for a policy workspace of its own, `_make_workspaces`."""
+    what = "the fused learner"
 
     def __init__(self, net, rows, steps, device):
         self.device = torch.device(device)
@@ -195,17 +201,33 @@ class FusedLearner:
         self.policy_flat, self.policy_grads = flat_gradients(self.policy_params)
         self.value_flat, self.value_grads = flat_gradients(self.value_params)
         self._L = _lib.lib()
-        need = 0
-        for params in (self.policy_params, self.value_params):
-            n = net_struct(params)
-            b = self._L.rex_ppo_workspace_bytes(self.rows, self.steps, n.obs_dim, n.out_dim, n.hidden1, n.hidden2)
-            if b < 0:
-                raise ValueError("the fused learner does not offer this shape: " + self._L.rex_last_error().decode("utf-8", "replace"))
-            need = max(need, b)
-        self.workspace = torch.empty(need // 4, dtype=torch.float32, device=self.device)
+        policy_bytes = self._policy_workspace_bytes(self._policy_net())
+        value_bytes = self._two_layer_workspace_bytes(net_struct(self.value_params)) if policy_bytes >= 0 else -1
+        if value_bytes < 0:
+            raise ValueError(self.what + " does not offer this shape: " + self._L.rex_last_error().decode("utf-8", "replace"))
+        self._make_workspaces(policy_bytes, value_bytes)
         self.length = torch.zeros(self.rows, dtype=torch.int32, device=self.device)
         self.kl_row = torch.zeros(self.rows, device=self.device)
         self._scratch_loss = torch.zeros(1, device=self.device)
+
+    def _two_layer_workspace_bytes(self, n):
+        return self._L.rex_ppo_workspace_bytes(self.rows, self.steps, n.obs_dim, n.out_dim, n.hidden1, n.hidden2)
+
+    def _policy_net(self):
+        return net_struct(self.policy_params)
+
+    def _policy_grad(self):
+        return grad_struct(self.policy_grads)
+
+    def _policy_workspace_bytes(self, n):
+        return self._two_layer_workspace_bytes(n)
+
+    def _policy_entry(self):
+        return self._L.rex_ppo_policy_loss, "rex_ppo_policy_loss"
+
+    def _make_workspaces(self, policy_bytes, value_bytes):
+        """one workspace: the policy and the value net take turns in it"""
+        self.workspace = self.policy_workspace = torch.empty(max(policy_bytes, value_bytes) // 4, dtype=torch.float32, device=self.device)
 
     def _stream(self):
         return ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
@@ -244,10 +266,11 @@ class FusedLearner:
         b, keep = self._batch(observ, action=action, old_mean=old_mean, old_logstd=old_logstd, advantage=advantage)
         b.penalty, b.kl_cutoff, b.kl_cutoff_coef = float(penalty), float(cutoff), float(coef)
         loss_out = self._scratch_loss if loss_out is None else loss_out
-        net, g = net_struct(self.policy_params), grad_struct(self.policy_grads)
+        net, g = self._policy_net(), self._policy_grad()
+        entry, name = self._policy_entry()
         with torch.cuda.device(self.device):
-            _lib.check(self._L.rex_ppo_policy_loss(ctypes.byref(net), ctypes.byref(b), ctypes.byref(g) if grad else None, loss_out.data_ptr(),
-                                                   self.kl_row.data_ptr(), self.workspace.data_ptr(), self._stream()), "rex_ppo_policy_loss")
+            _lib.check(entry(ctypes.byref(net), ctypes.byref(b), ctypes.byref(g) if grad else None, loss_out.data_ptr(), self.kl_row.data_ptr(),
+                             self.policy_workspace.data_ptr(), self._stream()), name)
         return loss_out, self.kl_row
 
     def value_loss(self, observ, return_, loss_out=None, grad=True, value_out=None):
@@ -271,33 +294,20 @@ class FusedLearner:
 class FusedRecurrentLearner(FusedLearner):
     """The same for a RecurrentGaussianPolicy: the policy loss runs on rex_ppo_recurrent_policy_loss (its own workspace: the stored activations
     of every memory slot), the value net and the return scans on FusedLearner's calls."""
+    what = "the fused recurrent learner"
 
-    def __init__(self, net, rows, steps, device):
-        self.device = torch.device(device)
-        self.rows, self.steps = int(rows), int(steps)
-        self.policy_params, self.value_params = net.policy_parameters(), net.value_parameters()
-        self.policy_flat, self.policy_grads = flat_gradients(self.policy_params)
-        self.value_flat, self.value_grads = flat_gradients(self.value_params)
-        self._L = _lib.lib()
-        n, v = rnn_net_struct(self.policy_params), net_struct(self.value_params)
-        need = [self._L.rex_ppo_recurrent_workspace_bytes(self.rows, self.steps, n.obs_dim, n.out_dim, n.hidden1, n.state)]
-        if need[0] >= 0:
-            need.append(self._L.rex_ppo_workspace_bytes(self.rows, self.steps, v.obs_dim, v.out_dim, v.hidden1, v.hidden2))
-        if need[-1] < 0:
-            raise ValueError("the fused recurrent learner does not offer this shape: " + self._L.rex_last_error().decode("utf-8", "replace"))
-        self.policy_workspace = torch.empty(need[0] // 4, dtype=torch.float32, device=self.device)
-        self.workspace = torch.empty(need[1] // 4, dtype=torch.float32, device=self.device)
-        self.length = torch.zeros(self.rows, dtype=torch.int32, device=self.device)
-        self.kl_row = torch.zeros(self.rows, device=self.device)
-        self._scratch_loss = torch.zeros(1, device=self.device)
+    def _policy_net(self):
+        return rnn_net_struct(self.policy_params)
 
-    def policy_loss(self, observ, action, old_mean, old_logstd, advantage, penalty, cutoff, coef, loss_out=None, grad=True):
-        b, keep = self._batch(observ, action=action, old_mean=old_mean, old_logstd=old_logstd, advantage=advantage)
-        b.penalty, b.kl_cutoff, b.kl_cutoff_coef = float(penalty), float(cutoff), float(coef)
-        loss_out = self._scratch_loss if loss_out is None else loss_out
-        net, g = rnn_net_struct(self.policy_params), rnn_grad_struct(self.policy_grads)
-        with torch.cuda.device(self.device):
-            _lib.check(self._L.rex_ppo_recurrent_policy_loss(ctypes.byref(net), ctypes.byref(b), ctypes.byref(g) if grad else None, loss_out.data_ptr(),
-                                                             self.kl_row.data_ptr(), self.policy_workspace.data_ptr(), self._stream()),
-                       "rex_ppo_recurrent_policy_loss")
-        return loss_out, self.kl_row
+    def _policy_grad(self):
+        return rnn_grad_struct(self.policy_grads)
+
+    def _policy_workspace_bytes(self, n):
+        return self._L.rex_ppo_recurrent_workspace_bytes(self.rows, self.steps, n.obs_dim, n.out_dim, n.hidden1, n.state)
+
+    def _policy_entry(self):
+        return self._L.rex_ppo_recurrent_policy_loss, "rex_ppo_recurrent_policy_loss"
+
+    def _make_workspaces(self, policy_bytes, value_bytes):
+        self.policy_workspace = torch.empty(policy_bytes // 4, dtype=torch.float32, device=self.device)
+        self.workspace = torch.empty(value_bytes // 4, dtype=torch.float32, device=self.device)

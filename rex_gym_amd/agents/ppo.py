@@ -263,12 +263,9 @@ class PPOAgent:
         self.n, self.device = num_agents, torch.device(device)
         if cfg.learner not in ("autograd", "fused", "fused_recurrent"):
             raise ValueError("PPOConfig.learner must be 'autograd', 'fused' or 'fused_recurrent'")
-        if cfg.learner == "fused":
+        if cfg.learner != "autograd":
             from .fused_learner import check_config
-            check_config(cfg, self.device)
-        if cfg.learner == "fused_recurrent":
-            from .fused_learner import check_config_recurrent
-            check_config_recurrent(cfg, self.device)
+            check_config(cfg, self.device, cfg.learner)
         gen = torch.Generator(device="cpu"); gen.manual_seed(seed)
         with torch.random.fork_rng(devices=[]):
             torch.manual_seed(seed)
@@ -292,12 +289,9 @@ class PPOAgent:
         self.value_opt = torch.optim.Adam(self.net.value_parameters(), lr=cfg.value_lr, eps=1e-8)
         self.sync_gradients = sync_gradients
         self._fused = None
-        if cfg.learner == "fused":
-            from .fused_learner import FusedLearner
-            self._fused = FusedLearner(self.net, cfg.update_every, T, self.device)
-        if cfg.learner == "fused_recurrent":
-            from .fused_learner import FusedRecurrentLearner
-            self._fused = FusedRecurrentLearner(self.net, cfg.update_every, T, self.device)
+        if cfg.learner != "autograd":
+            from .fused_learner import FusedLearner, FusedRecurrentLearner
+            self._fused = (FusedLearner if cfg.learner == "fused" else FusedRecurrentLearner)(self.net, cfg.update_every, T, self.device)
         self._full_episodes_unpolled, self._warned_unpolled = 0, False
         self.last = None
         self.updates = 0

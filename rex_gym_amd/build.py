@@ -2,7 +2,7 @@
 
 The library is compiled variant group by variant group -- one translation unit per group of rex_step_kernel /
 rex_settle_kernel instantiations (csrc/rex_step_*.hip, rex_settle_*.hip) next to the C ABI (csrc/rexsim.hip) -- in
-parallel, then linked (33 jobs, see variant_jobs(): every step unit once per mode it offers) where the single translation
+parallel, then linked (34 jobs, see variant_jobs(): every step unit once per mode it offers) where the single translation
 unit took over 2 minutes.
 
 Developer knobs (never needed for the product build):
@@ -22,11 +22,12 @@ CSRC = os.path.join(PKG_DIR, "csrc")
 LIB_PATH = os.environ.get("REX_LIB_PATH") or os.path.join(PKG_DIR, "librexsim_hip.so")   # REX_LIB_PATH: developer A/B builds
 # variant group names in the order of csrc/rex_kernels.h RexStepGroup (REX_BUILD_ONLY; the bit numbers of -DREX_LEFT_OUT_GROUPS)
 GROUP_NAMES = ["base", "arm", "mixed_base", "mixed_arm", "body"]
-# translation unit -> variant group name; rexsim.hip (C ABI, launcher table, reset and controller kernels) is always built
+# translation unit -> variant group name; rexsim.hip (the simulator's C ABI, launcher table, reset and controller kernels) and rex_learner.hip
+# (the fused PPO learners: their kernels and entry points) are always built
 GROUPS = {**{"rex_step_%s.hip" % g: g for g in GROUP_NAMES}, "rex_settle_base.hip": "base", "rex_settle_arm.hip": "arm"}
 # (the renderers -- rex_render, rex_render_visual -- are one kernel each, no variants; rexsim.hip last: a unity build includes it behind the
 # units whose launchers its table names)
-SOURCES = sorted(GROUPS) + ["rex_render.hip", "rex_render_mesh.hip", "rexsim.hip"]
+SOURCES = sorted(GROUPS) + ["rex_render.hip", "rex_render_mesh.hip", "rex_learner.hip", "rexsim.hip"]
 # the modes a step unit is compiled in (csrc/rex_kernels.h RexStepMode, where the reason for each is recorded) and their object-file tags
 MODES = {"STEP": "", "TRACE": "_trace", "SEG": "_seg", "POL": "_pol", "RNN": "_rnn"}
 

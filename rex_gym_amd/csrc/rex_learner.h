@@ -10,7 +10,7 @@
 //   2  h1 = relu(W1 x + b1)            one thread per unit, its row of W1 in registers
 //   3  h2 = relu(W2 h1 + b2)           v_mfma_f32_32x32x2_f32: wave w owns units 32 w .. 32 w + 31, both halves of the tile
 //   4  z = W3 h2 + b3                  one thread per (sample, output pair)
-//   5  the loss terms of the tile's samples and the seeds g_z of the backward pass (wave 0, one lane per sample)
+//   5  the loss terms of the tile's samples and the seeds g_z of the backward pass (wave 0, one lane per sample): ppo_gauss_terms / _seed
 //   6  dh2 = W3^T g_z . relu', dW3 += g_z^T h2, db2 += sum dh2    one thread per (unit, half tile); dh2 overwrites h2
 //   7  dW2 += dh2^T h1                 MFMA, K = the 64 samples; wave w owns input units 32 w .. and 32 (w + 4) .., 8 accumulator tiles
 //   8  dh1 = dh2 W2 . relu'            MFMA, K = H2; overwrites h1
@@ -21,6 +21,10 @@
 // 16-byte reads in flight per lane, out of two zero-padded copies the pack kernel writes in front of every call -- [H2p][H1p] for step 3,
 // its transpose [H1p][H2p] for step 8 -- so that a lane's four consecutive k are one read in both.  The k order inside a group of 8 is
 // permuted the same way for both operands (lane half h takes k = 8 g + 4 h + c at MFMA c of the group).
+//
+// Shared with rex_learner_rnn.h (one copy each): the Gaussian-policy loss head -- ppo_gauss_terms, ppo_gauss_seed, ppo_row_weight, ppo_row_loss --
+// the four-k MFMA block ppo_mfma_k4, ppo_row_len and the workgroup sum ppo_block_sum.  The build fixes arithmetic by source (-ffp-contract=on):
+// an expression moved into one of them keeps its spelling and with it every rounding.  The C ABI of both learners: rex_learner.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -84,6 +88,80 @@ __device__ __forceinline__ float ppo_wave_sum(float v) {     // a fixed tree ove
 }
 // the row of register e of lane half h in a 32 x 32 accumulator tile (the column is lane & 31)
 __device__ __forceinline__ int ppo_acc_row(int e, int h) { return (e & 3) + 8 * (e >> 2) + 4 * h; }
+// a row's length as every kernel reads it: inside [0, T]
+__device__ __forceinline__ int ppo_row_len(const int32_t* length, int r, int T) { return min(max(length[r], 0), T); }
+// four k of a product D[64][32] += A[64][k] B[32][k]: the two 32-row halves of A (x0, x1) against one B operand, k = the float4's lanes
+__device__ __forceinline__ void ppo_mfma_k4(ppo_f16& acc0, ppo_f16& acc1, const float4& x0, const float4& x1, const float4& b) {
+  acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(x0.x, b.x, acc0, 0, 0, 0); acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(x1.x, b.x, acc1, 0, 0, 0);
+  acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(x0.y, b.y, acc0, 0, 0, 0); acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(x1.y, b.y, acc1, 0, 0, 0);
+  acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(x0.z, b.z, acc0, 0, 0, 0); acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(x1.z, b.z, acc1, 0, 0, 0);
+  acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(x0.w, b.w, acc0, 0, 0, 0); acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(x1.w, b.w, acc1, 0, 0, 0);
+}
+// the sum of the workgroup's REX_PPO_THREADS values v at [0] of the returned LDS slots: a halving tree, the same order in every kernel.
+// A kernel with two sums gives each its own SLOT (its own 256 floats of LDS)
+template <int SLOT = 0>
+__device__ __forceinline__ const float* ppo_block_sum(int tid, float v) {
+  __shared__ float red[REX_PPO_THREADS];
+  red[tid] = v;
+  __syncthreads();
+  for (int m = REX_PPO_THREADS / 2; m >= 1; m >>= 1) {
+    if (tid < m) red[tid] += red[tid + m];
+    __syncthreads();
+  }
+  return red;
+}
+
+// ---- the Gaussian-policy loss head, shared with rex_learner_rnn.h: one sample's terms, its seeds, a row's weight and loss term ----
+struct PpoGauss { float m[REX_PPO_MAX_A], dm[REX_PPO_MAX_A], dx[REX_PPO_MAX_A], ie2[REX_PPO_MAX_A], ev[REX_PPO_MAX_A], u2[REX_PPO_MAX_A], kl, ratio; };   // (ev = e^(2 l0 - 2 l) - 1)
+// z [8]: the sample's pre-tanh means; at0: the float offset of its A actions in the [R][T][A] blocks; !valid: every term zero, nothing read
+__device__ __forceinline__ void ppo_gauss_terms(PpoGauss& h, const float* z, int A, bool valid, const float* __restrict__ logstd, const float* __restrict__ old_logstd,
+                                                const float* __restrict__ old_mean, const float* __restrict__ action, size_t at0) {
+  float kl = 0.0f, dlp = 0.0f;
+#pragma unroll
+  for (int a = 0; a < REX_PPO_MAX_A; ++a) {
+    h.m[a] = h.dm[a] = h.dx[a] = h.ie2[a] = h.ev[a] = h.u2[a] = 0.0f;
+    if (a < A && valid) {
+      const size_t at = at0 + a;
+      const float l = logstd[a], l0 = old_logstd[at], m0 = old_mean[at], x = action[at];
+      h.m[a] = tanhf(z[a]);
+      h.dm[a] = h.m[a] - m0; h.dx[a] = x - h.m[a];
+      h.ie2[a] = expf(-2.0f * l);
+      // e^d - 1 and e^d - 1 - d of d = 2 l0 - 2 l without the cancellation of their terms (the KL of two close policies is the small
+      // difference of numbers near 1): expm1f, and for small d the series d^2 / 2 (1 + d/3 (1 + d/4 (...)))
+      const float d = 2.0f * l0 - 2.0f * l;
+      h.ev[a] = expm1f(d);
+      const float series = 0.5f * d * d * (1.0f + d * (1.0f / 3.0f) * (1.0f + d * 0.25f * (1.0f + d * 0.2f * (1.0f + d * (1.0f / 6.0f) * (1.0f + d * (1.0f / 7.0f) * (1.0f + d * 0.125f))))));
+      const float phi = fabsf(d) < 0.25f ? series : h.ev[a] - d;
+      const float u = h.dx[a] * expf(-l), u0 = (x - m0) * expf(-l0);
+      h.u2[a] = u * u;
+      kl += phi + h.dm[a] * h.dm[a] * h.ie2[a];
+      dlp += -0.5f * (l - l0) - 0.5f * (h.u2[a] - u0 * u0);
+    }
+  }
+  kl *= 0.5f;
+  h.kl = kl;
+  h.ratio = expf(dlp);
+}
+// the seeds of output a: d loss / d z_a and d loss / d logstd_a of the sample (ra = ratio . advantage)
+__device__ __forceinline__ void ppo_gauss_seed(const PpoGauss& h, int a, float wr, float ra, float inv_rt, float* g_z, float* g_l) {
+  const float dkl_dm = h.dm[a] * h.ie2[a], dkl_dl = -h.ev[a] - h.dm[a] * h.dm[a] * h.ie2[a];
+  const float dlp_dm = h.dx[a] * h.ie2[a], dlp_dl = -0.5f + h.u2[a];
+  const float gm = inv_rt * (wr * dkl_dm - ra * dlp_dm), gl = inv_rt * (wr * dkl_dl - ra * dlp_dl);
+  *g_z = gm * (1.0f - h.m[a] * h.m[a]);
+  *g_l = gl;
+}
+// w_r = d (row loss) / d kl_r
+__device__ __forceinline__ float ppo_row_weight(float klr, float penalty, float cutoff, float coef) {
+  return penalty + (klr > cutoff ? 2.0f * coef * (klr - cutoff) : 0.0f);
+}
+// a row's loss term surrogate + penalty kl + coef [kl > c] (kl - c)^2 from its sums of KL and ratio . advantage over the steps; *kl_out = kl_r
+__device__ __forceinline__ float ppo_row_loss(float kl_sum, float sa_sum, int T, float penalty, float cutoff, float coef, float* kl_out) {
+  const float kl = kl_sum / (float)T, surrogate = -(sa_sum / (float)T);
+  const float over = kl - cutoff;
+  const float cut = kl > cutoff ? coef * (over * over) : 0.0f;
+  *kl_out = kl;
+  return surrogate + penalty * kl + cut;
+}
 
 // W2 [H2][H1] (torch) -> w2p [H2p][H1p] and w2t [H1p][H2p], zero beyond the layer's widths
 __global__ void rex_ppo_pack_kernel(const float* __restrict__ w2, int H1, int H2, int H1p, int H2p, float* __restrict__ w2p, float* __restrict__ w2t) {
@@ -134,7 +212,7 @@ __global__ __launch_bounds__(REX_PPO_THREADS) void rex_ppo_tile_kernel(PpoArgs p
   const int tiles = p.R * NT;
   for (int tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
     const int r = tile / NT, t0 = (tile - r * NT) * REX_PPO_TILE;
-    const int len = min(max(p.length[r], 0), T);
+    const int len = ppo_row_len(p.length, r, T);
     if (t0 >= len) continue;                     // (the same for every thread of the workgroup)
     const int nvalid = min(REX_PPO_TILE, len - t0);
     const size_t base = (size_t)r * T + t0;
@@ -183,10 +261,7 @@ __global__ __launch_bounds__(REX_PPO_THREADS) void rex_ppo_tile_kernel(PpoArgs p
           const float4 b = ring[u];
           ring[u] = bw[2 * min(g + 4, n - 1)];
           const float4 x0 = a0[2 * g], x1 = a1[2 * g];
-          acc[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(x0.x, b.x, acc[0], 0, 0, 0); acc[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(x1.x, b.x, acc[1], 0, 0, 0);
-          acc[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(x0.y, b.y, acc[0], 0, 0, 0); acc[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(x1.y, b.y, acc[1], 0, 0, 0);
-          acc[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(x0.z, b.z, acc[0], 0, 0, 0); acc[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(x1.z, b.z, acc[1], 0, 0, 0);
-          acc[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(x0.w, b.w, acc[0], 0, 0, 0); acc[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(x1.w, b.w, acc[1], 0, 0, 0);
+          ppo_mfma_k4(acc[0], acc[1], x0, x1, b);
         }
       }
 #pragma unroll
@@ -230,46 +305,24 @@ __global__ __launch_bounds__(REX_PPO_THREADS) void rex_ppo_tile_kernel(PpoArgs p
         if (lane == 0) p.part[tile] = sum;
         gz[0] = -d * p.inv_rt;
       } else {
-        float m[REX_PPO_MAX_A], dm[REX_PPO_MAX_A], dx[REX_PPO_MAX_A], ie2[REX_PPO_MAX_A], ev[REX_PPO_MAX_A], u2[REX_PPO_MAX_A];   // (ev = e^(2 l0 - 2 l) - 1)
-        float kl = 0.0f, dlp = 0.0f;
+        PpoGauss h;
+        float z[REX_PPO_MAX_A];
 #pragma unroll
-        for (int a = 0; a < REX_PPO_MAX_A; ++a) {
-          m[a] = dm[a] = dx[a] = ie2[a] = ev[a] = u2[a] = 0.0f;
-          if (a < A && valid) {
-            const size_t at = (base + s) * A + a;
-            const float l = p.logstd[a], l0 = p.old_logstd[at], m0 = p.old_mean[at], x = p.action[at];
-            m[a] = tanhf(zs[a * REX_PPO_TILE + s]);
-            dm[a] = m[a] - m0; dx[a] = x - m[a];
-            ie2[a] = expf(-2.0f * l);
-            // e^d - 1 and e^d - 1 - d of d = 2 l0 - 2 l without the cancellation of their terms (the KL of two close policies is the small
-            // difference of numbers near 1): expm1f, and for small d the series d^2 / 2 (1 + d/3 (1 + d/4 (...)))
-            const float d = 2.0f * l0 - 2.0f * l;
-            ev[a] = expm1f(d);
-            const float series = 0.5f * d * d * (1.0f + d * (1.0f / 3.0f) * (1.0f + d * 0.25f * (1.0f + d * 0.2f * (1.0f + d * (1.0f / 6.0f) * (1.0f + d * (1.0f / 7.0f) * (1.0f + d * 0.125f))))));
-            const float phi = fabsf(d) < 0.25f ? series : ev[a] - d;
-            const float u = dx[a] * expf(-l), u0 = (x - m0) * expf(-l0);
-            u2[a] = u * u;
-            kl += phi + dm[a] * dm[a] * ie2[a];
-            dlp += -0.5f * (l - l0) - 0.5f * (u2[a] - u0 * u0);
-          }
-        }
-        kl *= 0.5f;
-        const float ratio = expf(dlp);
+        for (int a = 0; a < REX_PPO_MAX_A; ++a) z[a] = (a < A && valid) ? zs[a * REX_PPO_TILE + s] : 0.0f;
+        ppo_gauss_terms(h, z, A, valid, p.logstd, p.old_logstd, p.old_mean, p.action, (base + s) * A);
+        const float kl = h.kl, ratio = h.ratio;
         const float adv = valid ? p.target[base + s] : 0.0f;
         if constexpr (!BWD) {
           const float ksum = ppo_wave_sum(valid ? kl : 0.0f), ssum = ppo_wave_sum(valid ? ratio * adv : 0.0f);
           if (lane == 0) { p.part[tile] = ksum; p.part[tiles + tile] = ssum; }
         } else {
-          const float klr = p.kl_row[r];
-          const float wr = p.penalty + (klr > p.cutoff ? 2.0f * p.coef * (klr - p.cutoff) : 0.0f);
+          const float wr = ppo_row_weight(p.kl_row[r], p.penalty, p.cutoff, p.coef);
           const float ra = ratio * adv;
 #pragma unroll
           for (int a = 0; a < REX_PPO_MAX_A; ++a) {
             if (a < A && valid) {
-              const float dkl_dm = dm[a] * ie2[a], dkl_dl = -ev[a] - dm[a] * dm[a] * ie2[a];
-              const float dlp_dm = dx[a] * ie2[a], dlp_dl = -0.5f + u2[a];
-              const float gm = p.inv_rt * (wr * dkl_dm - ra * dlp_dm), gl = p.inv_rt * (wr * dkl_dl - ra * dlp_dl);
-              gz[a] = gm * (1.0f - m[a] * m[a]);
+              float gl;
+              ppo_gauss_seed(h, a, wr, ra, p.inv_rt, &gz[a], &gl);
               gls[(REX_PPO_MAX_A + a) * REX_PPO_TILE + s] += gl;
             }
           }
@@ -350,15 +403,9 @@ __global__ __launch_bounds__(REX_PPO_THREADS) void rex_ppo_tile_kernel(PpoArgs p
               const float4 b0 = ring0[u], b1 = ring1[u];
               ring0[u] = bw0[2 * gn]; ring1[u] = bw1[2 * gn];
               const float4 x0 = a0[2 * g], x1 = a1[2 * g];
-              acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(x0.x, b0.x, acc[0][0], 0, 0, 0); acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(x1.x, b0.x, acc[0][1], 0, 0, 0);
-              acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(x0.y, b0.y, acc[0][0], 0, 0, 0); acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(x1.y, b0.y, acc[0][1], 0, 0, 0);
-              acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(x0.z, b0.z, acc[0][0], 0, 0, 0); acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(x1.z, b0.z, acc[0][1], 0, 0, 0);
-              acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(x0.w, b0.w, acc[0][0], 0, 0, 0); acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(x1.w, b0.w, acc[0][1], 0, 0, 0);
+              ppo_mfma_k4(acc[0][0], acc[0][1], x0, x1, b0);
               if (on1) {
-                acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(x0.x, b1.x, acc[1][0], 0, 0, 0); acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(x1.x, b1.x, acc[1][1], 0, 0, 0);
-                acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(x0.y, b1.y, acc[1][0], 0, 0, 0); acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(x1.y, b1.y, acc[1][1], 0, 0, 0);
-                acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(x0.z, b1.z, acc[1][0], 0, 0, 0); acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(x1.z, b1.z, acc[1][1], 0, 0, 0);
-                acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(x0.w, b1.w, acc[1][0], 0, 0, 0); acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(x1.w, b1.w, acc[1][1], 0, 0, 0);
+                ppo_mfma_k4(acc[1][0], acc[1][1], x0, x1, b1);
               }
             }
           }
@@ -438,28 +485,21 @@ __global__ __launch_bounds__(REX_PPO_THREADS) void rex_ppo_tile_kernel(PpoArgs p
 // the per-tile sums -> kl_row [R] and the scalar loss, in a fixed order: one workgroup, a thread adds its rows' tiles, then a tree
 template <bool VALUE>
 __global__ __launch_bounds__(REX_PPO_THREADS) void rex_ppo_rows_kernel(PpoArgs p, float* __restrict__ loss, float* __restrict__ kl_row) {
-  __shared__ float red[REX_PPO_THREADS];
   const int tid = threadIdx.x, tiles = p.R * p.NT;
   float acc = 0.0f;
   for (int r = tid; r < p.R; r += REX_PPO_THREADS) {
-    const int len = min(max(p.length[r], 0), p.T), nt = (len + REX_PPO_TILE - 1) / REX_PPO_TILE;
+    const int len = ppo_row_len(p.length, r, p.T), nt = (len + REX_PPO_TILE - 1) / REX_PPO_TILE;
     float a = 0.0f, b = 0.0f;
     for (int k = 0; k < nt; ++k) { a += p.part[r * p.NT + k]; if (!VALUE) b += p.part[tiles + r * p.NT + k]; }
     if (VALUE) acc += a;
     else {
-      const float kl = a / (float)p.T, surrogate = -(b / (float)p.T);
-      const float over = kl - p.cutoff;
-      const float cut = kl > p.cutoff ? p.coef * (over * over) : 0.0f;
+      float kl;
+      const float term = ppo_row_loss(a, b, p.T, p.penalty, p.cutoff, p.coef, &kl);
       kl_row[r] = kl;
-      acc += surrogate + p.penalty * kl + cut;
+      acc += term;
     }
   }
-  red[tid] = acc;
-  __syncthreads();
-  for (int m = REX_PPO_THREADS / 2; m >= 1; m >>= 1) {
-    if (tid < m) red[tid] += red[tid + m];
-    __syncthreads();
-  }
+  const float* red = ppo_block_sum(tid, acc);
   if (tid == 0) *loss = VALUE ? red[0] / ((float)p.R * (float)p.T) : red[0] / (float)p.R;
 }
 

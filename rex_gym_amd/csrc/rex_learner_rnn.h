@@ -1,6 +1,7 @@
 // rex_learner_rnn.h -- the policy loss of the reference's RECURRENT agent (networks.py:113-159: O -> F -> GRU(100) -> A) over the episode memory and
 // its nine parameter gradients by backpropagation through time, as kernels (rex_ppo_recurrent_policy_loss).  fp32 throughout; sigmoid and
 // tanh from expf / tanhf.  Formulas: include/rexsim.h.  Every sum runs in a fixed order, no atomics: two calls return the same bits.
+// The loss head, the MFMA block, the row length and the workgroup sum are rex_learner.h's helpers; the entry point is in rex_learner.hip.
 //
 // Decomposition.  Wg = [Wgx | Wgh], Wc = [Wcx | Wch].  Whatever does not depend on the recurrence is a product over 64-step tiles of one
 // episode row (tiles wholly beyond the row's length are skipped, steps beyond it masked); only the H x 3H part is a scan over t.
@@ -77,7 +78,7 @@ struct RnnGradDev { float *w1, *b1, *wg, *bg, *wc, *bc, *wm, *bm, *logstd; };
 // the tile's row, first step and number of valid steps (0: skip it)
 __device__ __forceinline__ int rnn_tile(const RnnArgs& p, int tile, size_t* base) {
   const int r = tile / p.NT, t0 = (tile - r * p.NT) * REX_PPO_TILE;
-  const int len = min(max(p.length[r], 0), p.T);
+  const int len = ppo_row_len(p.length, r, p.T);
   *base = (size_t)r * p.T + t0;
   return t0 >= len ? 0 : min(REX_PPO_TILE, len - t0);
 }
@@ -113,7 +114,7 @@ __global__ __launch_bounds__(256) void rex_rnn_input_kernel(RnnArgs p) {
   const size_t n = idx / p.Fp;
   if (n >= (size_t)p.R * p.T) return;
   const int f = (int)(idx - n * p.Fp), r = (int)(n / p.T), t = (int)(n - (size_t)r * p.T);
-  if (t >= min(max(p.length[r], 0), p.T)) return;
+  if (t >= ppo_row_len(p.length, r, p.T)) return;
   float acc = 0.0f;
   if (f < p.F) {
     // a compensated dot product (Ogita, Rump, Oishi: Dot2 -- every product's and every sum's rounding error carried along in fp32): the
@@ -157,10 +158,7 @@ __global__ __launch_bounds__(256) void rex_rnn_rows_kernel(RnnArgs p) {
 #pragma unroll 4
     for (int g = 0; g < K / 8; ++g) {
       const float4 x0 = a0[2 * g], x1 = a1[2 * g], b = bw[2 * g];
-      acc[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(x0.x, b.x, acc[0], 0, 0, 0); acc[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(x1.x, b.x, acc[1], 0, 0, 0);
-      acc[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(x0.y, b.y, acc[0], 0, 0, 0); acc[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(x1.y, b.y, acc[1], 0, 0, 0);
-      acc[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(x0.z, b.z, acc[0], 0, 0, 0); acc[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(x1.z, b.z, acc[1], 0, 0, 0);
-      acc[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(x0.w, b.w, acc[0], 0, 0, 0); acc[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(x1.w, b.w, acc[1], 0, 0, 0);
+      ppo_mfma_k4(acc[0], acc[1], x0, x1, b);
     }
     const int col = 32 * ut + r32;
     const float bias = BWD ? 0.0f : p.biasp[col];
@@ -188,7 +186,7 @@ __global__ __launch_bounds__(REX_RNN_SCAN_THREADS) void rex_rnn_scan_fwd_kernel(
   float* us = rhs + H * G;
   for (int i = tid; i < 3 * H * H; i += REX_RNN_SCAN_THREADS) wt[i] = p.wht[i];
   for (int i = tid; i < 3 * H * G; i += REX_RNN_SCAN_THREADS) hs[i] = 0.0f;
-  if (tid < G) lens[tid] = r0 + tid < p.R ? min(max(p.length[r0 + tid], 0), T) : 0;
+  if (tid < G) lens[tid] = r0 + tid < p.R ? ppo_row_len(p.length, r0 + tid, T) : 0;
   __syncthreads();
   int lmax = 0;
 #pragma unroll
@@ -254,13 +252,13 @@ __global__ __launch_bounds__(REX_RNN_SCAN_THREADS) void rex_rnn_scan_fwd_kernel(
   }
 }
 
-// one thread per valid step: the mean, the loss terms (!BWD) or the seeds (BWD).  The loss arithmetic is rex_ppo_tile_kernel's step 5.
+// one thread per valid step: the mean, the loss terms (!BWD) or the seeds (BWD): the loss head of rex_learner.h on a register z
 template <bool BWD>
 __global__ __launch_bounds__(256) void rex_rnn_head_kernel(RnnArgs p) {
   const size_t n = (size_t)blockIdx.x * 256 + threadIdx.x;
   if (n >= (size_t)p.R * p.T) return;
   const int r = (int)(n / p.T), t = (int)(n - (size_t)r * p.T), A = p.A;
-  if (t >= min(max(p.length[r], 0), p.T)) return;
+  if (t >= ppo_row_len(p.length, r, p.T)) return;
   float z[REX_PPO_MAX_A];
 #pragma unroll
   for (int a = 0; a < REX_PPO_MAX_A; ++a) z[a] = a < A ? p.bm[a] : 0.0f;
@@ -274,42 +272,21 @@ __global__ __launch_bounds__(256) void rex_rnn_head_kernel(RnnArgs p) {
         z[a] = fmaf(w[0], h.x, z[a]); z[a] = fmaf(w[1], h.y, z[a]); z[a] = fmaf(w[2], h.z, z[a]); z[a] = fmaf(w[3], h.w, z[a]);
       }
   }
-  float m[REX_PPO_MAX_A], dm[REX_PPO_MAX_A], dx[REX_PPO_MAX_A], ie2[REX_PPO_MAX_A], ev[REX_PPO_MAX_A], u2[REX_PPO_MAX_A];
-  float kl = 0.0f, dlp = 0.0f;
-#pragma unroll
-  for (int a = 0; a < REX_PPO_MAX_A; ++a) {
-    m[a] = dm[a] = dx[a] = ie2[a] = ev[a] = u2[a] = 0.0f;
-    if (a < A) {
-      const size_t at = n * A + a;
-      const float l = p.logstd[a], l0 = p.old_logstd[at], m0 = p.old_mean[at], x = p.action[at];
-      m[a] = tanhf(z[a]);
-      dm[a] = m[a] - m0; dx[a] = x - m[a];
-      ie2[a] = expf(-2.0f * l);
-      const float d = 2.0f * l0 - 2.0f * l;
-      ev[a] = expm1f(d);
-      const float series = 0.5f * d * d * (1.0f + d * (1.0f / 3.0f) * (1.0f + d * 0.25f * (1.0f + d * 0.2f * (1.0f + d * (1.0f / 6.0f) * (1.0f + d * (1.0f / 7.0f) * (1.0f + d * 0.125f))))));
-      const float phi = fabsf(d) < 0.25f ? series : ev[a] - d;
-      const float u = dx[a] * expf(-l), u0 = (x - m0) * expf(-l0);
-      u2[a] = u * u;
-      kl += phi + dm[a] * dm[a] * ie2[a];
-      dlp += -0.5f * (l - l0) - 0.5f * (u2[a] - u0 * u0);
-    }
-  }
-  kl *= 0.5f;
-  const float ra = expf(dlp) * p.advantage[n];
+  PpoGauss h;
+  ppo_gauss_terms(h, z, A, true, p.logstd, p.old_logstd, p.old_mean, p.action, n * A);
+  const float kl = h.kl;
+  const float ra = h.ratio * p.advantage[n];
   if constexpr (!BWD) {
     p.klt[n] = kl;
     p.sat[n] = ra;
   } else {
-    const float klr = p.kl_row[r];
-    const float wr = p.penalty + (klr > p.cutoff ? 2.0f * p.coef * (klr - p.cutoff) : 0.0f);
+    const float wr = ppo_row_weight(p.kl_row[r], p.penalty, p.cutoff, p.coef);
     float out[16];
 #pragma unroll
     for (int a = 0; a < REX_PPO_MAX_A; ++a) {
-      const float dkl_dm = dm[a] * ie2[a], dkl_dl = -ev[a] - dm[a] * dm[a] * ie2[a];
-      const float dlp_dm = dx[a] * ie2[a], dlp_dl = -0.5f + u2[a];
-      const float gm = p.inv_rt * (wr * dkl_dm - ra * dlp_dm), gl = p.inv_rt * (wr * dkl_dl - ra * dlp_dl);
-      out[a] = a < A ? gm * (1.0f - m[a] * m[a]) : 0.0f;
+      float gz, gl;
+      ppo_gauss_seed(h, a, wr, ra, p.inv_rt, &gz, &gl);
+      out[a] = a < A ? gz : 0.0f;
       out[8 + a] = a < A ? gl : 0.0f;
     }
     float4* o4 = reinterpret_cast<float4*>(p.gzl + n * 16);
@@ -319,35 +296,24 @@ __global__ __launch_bounds__(256) void rex_rnn_head_kernel(RnnArgs p) {
 }
 
 // one workgroup per row: its steps' terms, a thread's in step order, then a tree -> kl_row, the row's loss term
-__global__ __launch_bounds__(256) void rex_rnn_rowsum_kernel(RnnArgs p, float* __restrict__ kl_row) {
-  __shared__ float ra[256], rb[256];
-  const int tid = threadIdx.x, r = blockIdx.x, len = min(max(p.length[r], 0), p.T);
+__global__ __launch_bounds__(REX_PPO_THREADS) void rex_rnn_rowsum_kernel(RnnArgs p, float* __restrict__ kl_row) {
+  const int tid = threadIdx.x, r = blockIdx.x, len = ppo_row_len(p.length, r, p.T);
   float a = 0.0f, b = 0.0f;
-  for (int t = tid; t < len; t += 256) { a += p.klt[(size_t)r * p.T + t]; b += p.sat[(size_t)r * p.T + t]; }
-  ra[tid] = a; rb[tid] = b;
-  __syncthreads();
-  for (int m = 128; m >= 1; m >>= 1) {
-    if (tid < m) { ra[tid] += ra[tid + m]; rb[tid] += rb[tid + m]; }
-    __syncthreads();
-  }
+  for (int t = tid; t < len; t += REX_PPO_THREADS) { a += p.klt[(size_t)r * p.T + t]; b += p.sat[(size_t)r * p.T + t]; }
+  const float* ra = ppo_block_sum<0>(tid, a);
+  const float* rb = ppo_block_sum<1>(tid, b);
   if (tid == 0) {
-    const float kl = ra[0] / (float)p.T, surrogate = -(rb[0] / (float)p.T);
-    const float over = kl - p.cutoff;
+    float kl;
+    const float term = ppo_row_loss(ra[0], rb[0], p.T, p.penalty, p.cutoff, p.coef, &kl);
     kl_row[r] = kl;
-    p.rowloss[r] = surrogate + p.penalty * kl + (kl > p.cutoff ? p.coef * (over * over) : 0.0f);
+    p.rowloss[r] = term;
   }
 }
-__global__ __launch_bounds__(256) void rex_rnn_loss_kernel(RnnArgs p, float* __restrict__ loss) {
-  __shared__ float red[256];
+__global__ __launch_bounds__(REX_PPO_THREADS) void rex_rnn_loss_kernel(RnnArgs p, float* __restrict__ loss) {
   const int tid = threadIdx.x;
   float acc = 0.0f;
-  for (int r = tid; r < p.R; r += 256) acc += p.rowloss[r];
-  red[tid] = acc;
-  __syncthreads();
-  for (int m = 128; m >= 1; m >>= 1) {
-    if (tid < m) red[tid] += red[tid + m];
-    __syncthreads();
-  }
+  for (int r = tid; r < p.R; r += REX_PPO_THREADS) acc += p.rowloss[r];
+  const float* red = ppo_block_sum(tid, acc);
   if (tid == 0) *loss = red[0] / (float)p.R;
 }
 
@@ -363,7 +329,7 @@ __global__ __launch_bounds__(REX_RNN_SCAN_THREADS) void rex_rnn_scan_bwd_kernel(
   float* dag = dac + H * G;
   for (int i = tid; i < 3 * H * H; i += REX_RNN_SCAN_THREADS) w[i] = p.wh[i];
   for (int i = tid; i < REX_PPO_MAX_A * H; i += REX_RNN_SCAN_THREADS) wms[i] = i < A * H ? p.wm[i] : 0.0f;
-  if (tid < G) lens[tid] = r0 + tid < p.R ? min(max(p.length[r0 + tid], 0), T) : 0;
+  if (tid < G) lens[tid] = r0 + tid < p.R ? ppo_row_len(p.length, r0 + tid, T) : 0;
   __syncthreads();
   int lmax = 0;
 #pragma unroll

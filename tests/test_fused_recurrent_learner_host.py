@@ -8,7 +8,7 @@ import torch
 
 from rex_gym_amd.agents import PPOAgent, PPOConfig
 
-import fused_recurrent_cases as rc
+import fused_cases as fc
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ENTRY_POINTS = ("rex_ppo_recurrent_workspace_bytes", "rex_ppo_recurrent_policy_loss")
@@ -19,16 +19,16 @@ def test_backward_recurrence_matches_fp64_autograd(shape):
     """The nine gradient tensors and kl_row of `_update_policy`'s loss through the GRU: recurrent_backward (no autograd) against fp64 autograd
     of RecurrentGaussianPolicy, max|diff| / max|ref| <= 1e-12 per tensor; rows on both sides of the KL cutoff, so the w_r term is tested."""
     from rex_gym_amd.agents.fused_learner import recurrent_backward
-    c = rc.to(rc.make_case(shape, 4, 2), "cpu", torch.float64)
-    want = rc.autograd(c, "cpu", torch.float64)
+    c = fc.to(fc.make_case("recurrent", shape, 4, 2), "cpu", torch.float64)
+    want = fc.autograd(c, "cpu", torch.float64)
     kl = want["kl_row"]
-    above, below = int((kl > rc.CUTOFF).sum()), int((kl <= rc.CUTOFF).sum())
+    above, below = int((kl > fc.CUTOFF).sum()), int((kl <= fc.CUTOFF).sum())
     print("%s: %d rows above the cutoff, %d at or below" % (shape, above, below))
     assert above >= 1 and below >= 1, kl
-    p = dict(zip(rc.NAMES, [q.detach() for q in c["net"].policy_parameters()]))
+    p = dict(zip(fc.NAMES["recurrent"], [q.detach() for q in c["net"].policy_parameters()]))
     grads, kl_row = recurrent_backward(p["w1"], p["b1"], p["wg"], p["bg"], p["wc"], p["bc"], p["wm"], p["bm"], p["logstd"], c["observ"], c["old_mean"],
-                                       c["old_logstd"], c["action"], c["advantage"], c["length"], rc.PENALTY, rc.CUTOFF, rc.COEF)
-    for name, ref in list(zip(rc.NAMES, want["policy_grads"])) + [("kl_row", kl)]:
+                                       c["old_logstd"], c["action"], c["advantage"], c["length"], fc.PENALTY, fc.CUTOFF, fc.COEF)
+    for name, ref in list(zip(fc.NAMES["recurrent"], want["policy_grads"])) + [("kl_row", kl)]:
         got = kl_row if name == "kl_row" else grads[name]
         err = float((got - ref).abs().max() / ref.abs().max())
         print("%s %s: %.3e" % (shape, name, err))

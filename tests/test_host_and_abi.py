@@ -35,8 +35,8 @@ def test_library_exports_every_declared_symbol(L):
 def test_build_matrix_is_the_offered_variants():
     """build.variant_jobs() is the one list the object build, the unity build and the flags stamp are driven by: every step unit once per
     (mode, MOTOR) that csrc/rex_kernels.h rex_step_variant_offered offers -- the fused actors (POL, RNN) for base and arm only, the
-    actuator parameters (MOT) for SEG, POL and RNN only -- plus the two settle units, the renderers and the C ABI.  33 objects: 28 step
-    jobs + 2 settle + 3 others.  The expected set is spelled out so that a change of the rule is a visible diff."""
+    actuator parameters (MOT) for SEG, POL and RNN only -- plus the two settle units, the renderers, the learners and the C ABI.  34 objects: 28 step
+    jobs + 2 settle + 4 others.  The expected set is spelled out so that a change of the rule is a visible diff."""
     from rex_gym_amd import build
     all5 = ["arm", "base", "body", "mixed_arm", "mixed_base"]
     single = ["arm", "base"]
@@ -48,10 +48,10 @@ def test_build_matrix_is_the_offered_variants():
         defines = ([] if mode is None else ["-DREX_TU_MODE=REX_MODE_" + mode]) + (["-DREX_TU_MOT=1"] if mot else [])
         expected |= {("rex_step_%s.hip" % g, tuple(sorted(defines))) for g in groups}
     assert len(expected) == 5 + 5 + 5 + 2 + 2 + 5 + 2 + 2 == 28
-    expected |= {(s, ()) for s in ("rex_settle_arm.hip", "rex_settle_base.hip", "rex_render.hip", "rex_render_mesh.hip", "rexsim.hip")}
+    expected |= {(s, ()) for s in ("rex_settle_arm.hip", "rex_settle_base.hip", "rex_render.hip", "rex_render_mesh.hip", "rex_learner.hip", "rexsim.hip")}
     jobs = build.variant_jobs()
     pairs = [(s, tuple(sorted(d))) for s, _, d in jobs]
-    assert len(jobs) == 33 and len(set(pairs)) == len(pairs)
+    assert len(jobs) == 34 and len(set(pairs)) == len(pairs)
     assert set(pairs) == expected, set(pairs) ^ expected
     objects = [s[:-4] + tag for s, tag, _ in jobs]
     assert len(set(objects)) == len(objects)          # the tags keep the object files apart
