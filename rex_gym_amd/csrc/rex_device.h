@@ -1467,7 +1467,7 @@ __device__ __forceinline__ void physics_substep(PhysState& s, float* tau, float 
                                                 unsigned* trace = nullptr, int trace_n = 0, int env = 0, bool live = false) {
   // TRACE (the kernel instantiations launched while rex_set_event_trace is on; the product kernels carry none of it): `trace` =
   // the event trace buffer [3][trace_n]; `live`: this lane stores env's words
-  // lane_sweeps: += the solver sweeps THIS env ran (the host regroups large batches by it, rex_regroup_kernel)
+  // lane_sweeps: += the solver sweeps THIS env ran (the host regroups large batches by it, rex_regroup_count_kernel)
   // `iterations`: wave-uniform sweep cap; `lane_iterations` <= iterations: this env's own cap (they differ only in a batch
   // that mixes tasks with different numSolverIterations, REX_TASK_MIXED)
   REX_STAMP(t_begin);

@@ -17,6 +17,7 @@
 #include <string.h>
 #include <math.h>
 #include <stdlib.h>
+#include "rex_philox.h"
 
 // Floating-point contraction is fixed BY THE SOURCE, for every translation unit of the library and every tool that compiles one
 // (tools/kres.sh, kstat.sh, check_dpp_masks.py): `a * b + c` inside one expression is one fma, nothing else is fused.  hipcc's
@@ -196,17 +197,7 @@ __device__ __forceinline__ void euler_to_row2(const float* rpy, float& r20, floa
   r20 = x * zs - w * ys; r21 = y * zs + w * xs; r22 = 1.0f - (x * xs + y * ys);
 }
 
-// ---- Philox4x32-10 ----
-__device__ __forceinline__ void philox4x32(uint32_t* c, uint32_t k0, uint32_t k1) {
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const uint32_t h0 = __umulhi(0xD2511F53u, c[0]), l0 = 0xD2511F53u * c[0];
-    const uint32_t h1 = __umulhi(0xCD9E8D57u, c[2]), l1 = 0xCD9E8D57u * c[2];
-    const uint32_t n0 = h1 ^ c[1] ^ k0, n1 = l1, n2 = h0 ^ c[3] ^ k1, n3 = l0;
-    c[0] = n0; c[1] = n1; c[2] = n2; c[3] = n3;
-    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-  }
-}
+// ---- Philox4x32-10: rex_philox.h ----
 __device__ __forceinline__ float u01(uint32_t x) { return (float)(x >> 8) * (1.0f / 16777216.0f); }
 // Four standard normal draws (Box-Muller on one Philox block) for the sensor-noise model: Rex._AddSensorNoise
 // (model/rex.py:765-769) draws np.random.normal afresh in every getter call; here a getter call site of a step is one or
@@ -307,9 +298,7 @@ __host__ __device__ __forceinline__ float task_energy_weight(int task) { return 
 
 // the task env `gidx` runs for its whole life in a REX_TASK_MIXED batch: a draw from its own Philox stream
 __device__ __forceinline__ int mixed_task_of(const DevCfg& c, int gidx) {
-  uint32_t ctr[4] = {0xFFFFFFFFu, (uint32_t)gidx, 2u, 0u};
-  philox4x32(ctr, c.seed_lo, c.seed_hi);
-  const int k = (int)(ctr[0] % (uint32_t)c.n_mix);
+  const int k = mixed_task_draw(c.seed_lo, c.seed_hi, gidx, c.n_mix);
   return k == 0 ? c.mix_task[0] : (k == 1 ? c.mix_task[1] : (k == 2 ? c.mix_task[2] : (k == 3 ? c.mix_task[3] : c.mix_task[4])));
 }
 
@@ -1367,7 +1356,9 @@ __global__ void rex_reset_kernel(DevCfg c, float* __restrict__ state, const floa
 
 }  // namespace rex
 
-namespace rex { struct MixRegions { int32_t n_mix, bins_per_task, base[5]; }; }   // base[k]: first slot of task slot k's region of the slot map
+// the key of the per-step counting sort (rexsim.hip rex_regroup_*): an env's bin is its class's bins_per_class sweep bins of bin_width
+// sweeps each, class k fills the slots from base[k]; cls[i] = class of env i (null: one class)
+namespace rex { struct RegroupKey { int32_t bin_width, bins_per_class, n_classes, base[5]; const int32_t* cls; }; }
 // ---- host side shared by the translation units ----
 #define REX_TIMING_RING 256     /* event pairs of rex_set_timing(2) */
 struct RexSim {
@@ -1392,8 +1383,8 @@ struct RexSim {
   int32_t* d_slot_env;   // REX_TASK_MIXED: the task-sorted slot map (DevCfg::slot_env / block_task) and its workgroup count
   int32_t* d_block_task;
   int mixed_blocks;
-  int32_t* d_class;      // a regrouped mixed batch: task slot of every env (rexsim.hip, rex_regroup_mixed_*), and its regions
-  rex::MixRegions mix_regions;
+  int32_t* d_class;      // a regrouped mixed batch: task slot of every env, the classes of its sort
+  rex::RegroupKey regroup_key;   // the sort of a sim that regroups (d_regroup): one class from slot 0, or the mix's tasks and their regions
   rex::MotDev mot;       // rex_set_motor_params / rex_set_motor_randomization: set -> the MOTOR instantiations are launched
   rex::PolDev pol;       // rex_set_policy: the actor of rex_step_policy / rex_step_segment_policy
   float* d_polbuf;       // the packed actor (library-owned; rex_policy.h policy_offsets) and its capacity in floats

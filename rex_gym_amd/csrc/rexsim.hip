@@ -2,9 +2,11 @@
 // gfx950 only.  Build: hipcc --offload-arch=gfx950 -O3 -std=c++17 -shared -fPIC rexsim.hip -o librexsim_hip.so
 //
 // The step and settle kernels are instantiated in rex_step_*.hip / rex_settle.hip (rex_kernels.h); this file holds the
-// simulator's C ABI, the reset kernel and the small kernels (regrouping, controller-only entry points).  The fused PPO learners'
-// entry points are rex_learner.hip's; rex_last_error and the message both units set (rex_error.h) live here.
+// simulator's C ABI, the reset kernel and the small kernels (the regrouping sort rex_regroup_count_kernel / rex_regroup_scatter_kernel,
+// controller-only entry points).  Which envs of a mixed batch share a wave is host code of its own (rex_placement.h).  The fused PPO
+// learners' entry points are rex_learner.hip's; rex_last_error and the message both units set (rex_error.h) live here.
 #include "rex_kernels.h"
+#include "rex_placement.h"
 #include "rex_render.h"
 #include "rex_visual_gen.h"
 #include "rex_error.h"
@@ -78,27 +80,22 @@ __global__ void rex_zero_rnn_state_kernel(float* __restrict__ state, int n, int 
 }
 
 
-// Regrouping of a large batch (one workgroup): counting sort of the env indices by the solver sweeps of the last step,
-// most sweeps first (the long waves start first), 64 bins.  perm[k] = env of wave slot k.  The order inside a bin does
-// not matter: an env's result does not depend on its wave-mates.
-__global__ __launch_bounds__(1024) void rex_regroup_kernel(int n, int bin_width, const int32_t* __restrict__ sweeps, int32_t* __restrict__ perm) {
-  __shared__ int hist[64], base[64];
-  const int t = threadIdx.x;
-  if (t < 64) hist[t] = 0;
-  __syncthreads();
-  for (int i = t; i < n; i += 1024) atomicAdd(&hist[63 - min(sweeps[i] / bin_width, 63)], 1);
-  __syncthreads();
-  if (t == 0) { int acc = 0; for (int b = 0; b < 64; ++b) { base[b] = acc; acc += hist[b]; } }
-  __syncthreads();
-  for (int i = t; i < n; i += 1024) perm[atomicAdd(&base[63 - min(sweeps[i] / bin_width, 63)], 1)] = i;
-}
-// The same sort over many workgroups (the one-workgroup kernel above takes 0.3 ms for 262 144 envs: a tenth of their step):
-// workgroup b counts its REX_REGROUP_CHUNK envs per bin; the last workgroup to finish turns the counts into start offsets
-// (bins in order, workgroups in order inside a bin: the permutation is the one-workgroup kernel's up to the order inside a
-// bin); a second launch scatters.
+// Regrouping: a counting sort of the env indices by the solver sweeps of the last step, most sweeps first (the long waves start
+// first), 64 bins, over many workgroups (one workgroup takes 0.3 ms for 262 144 envs: a tenth of their step).  The order inside
+// a bin does not matter: an env's result does not depend on its wave-mates.
+//   a single-task batch: one class of 64 bins from slot 0; out = DevCfg::perm, perm[k] = env of wave slot k.
+//   a REX_TASK_MIXED batch: every task of the mix is a class and owns a STATIC region of the slot map (whole waves; the envs keep
+//   their task for life, so the region sizes and its padding slots never change); inside its region a task's envs are sorted --
+//   the waves of a large mixed batch then hold envs that need about the same number of sweeps, and the waves that exceed one
+//   round of the machine are the short ones.  64 / n_mix sweep bins per task; out = DevCfg::slot_env.
+// Workgroup b counts its REX_REGROUP_CHUNK envs per bin; the last workgroup to finish turns the counts into start offsets (a
+// class's bins fill its region from its first slot, bins in order, workgroups in order inside a bin); a second launch scatters.
 #define REX_REGROUP_CHUNK 1024
-__device__ __forceinline__ int regroup_bin(int sweeps, int bin_width) { return 63 - min(sweeps / bin_width, 63); }
-__global__ __launch_bounds__(256) void rex_regroup_count_kernel(int n, int bin_width, const int32_t* __restrict__ sweeps, int32_t* __restrict__ counts,
+__device__ __forceinline__ int regroup_bin(const RegroupKey& key, int sweeps, int i) {
+  const int w = key.bins_per_class;
+  return (key.cls ? key.cls[i] : 0) * w + (w - 1 - min(sweeps / key.bin_width, w - 1));
+}
+__global__ __launch_bounds__(256) void rex_regroup_count_kernel(int n, RegroupKey key, const int32_t* __restrict__ sweeps, int32_t* __restrict__ counts,
                                                                 unsigned* __restrict__ done) {
   __shared__ int hist[64];
   __shared__ bool last;
@@ -107,7 +104,7 @@ __global__ __launch_bounds__(256) void rex_regroup_count_kernel(int n, int bin_w
   __syncthreads();
   for (int k = t; k < REX_REGROUP_CHUNK; k += 256) {
     const int i = b * REX_REGROUP_CHUNK + k;
-    if (i < n) atomicAdd(&hist[regroup_bin(sweeps[i], bin_width)], 1);
+    if (i < n) atomicAdd(&hist[regroup_bin(key, sweeps[i], i)], 1);
   }
   __syncthreads();
   if (t < 64) counts[b * 64 + t] = hist[t];
@@ -121,74 +118,30 @@ __global__ __launch_bounds__(256) void rex_regroup_count_kernel(int n, int bin_w
   __shared__ int total[64], first[64];
   if (t < 64) { int acc = 0; for (int k = 0; k < nb; ++k) acc += counts[k * 64 + t]; total[t] = acc; }
   __syncthreads();
-  if (t == 0) { int acc = 0; for (int k = 0; k < 64; ++k) { first[k] = acc; acc += total[k]; } *done = 0u; }
-  __syncthreads();
-  if (t < 64) { int acc = first[t]; for (int k = 0; k < nb; ++k) { const int c = counts[k * 64 + t]; counts[k * 64 + t] = acc; acc += c; } }
-}
-__global__ __launch_bounds__(256) void rex_regroup_scatter_kernel(int n, int bin_width, const int32_t* __restrict__ sweeps, const int32_t* __restrict__ counts,
-                                                                  int32_t* __restrict__ perm) {
-  __shared__ int cursor[64];
-  const int t = threadIdx.x, b = blockIdx.x;
-  if (t < 64) cursor[t] = counts[b * 64 + t];
-  __syncthreads();
-  for (int k = t; k < REX_REGROUP_CHUNK; k += 256) {
-    const int i = b * REX_REGROUP_CHUNK + k;
-    if (i < n) perm[atomicAdd(&cursor[regroup_bin(sweeps[i], bin_width)], 1)] = i;
-  }
-}
-// Regrouping of a REX_TASK_MIXED batch: every task of the mix owns a STATIC region of the slot map (whole waves; the envs keep
-// their task for life, so the region sizes and its padding slots never change); inside its region a task's envs are sorted by
-// the sweeps of their last step, most first -- the waves of a large mixed batch then hold envs that need about the same number
-// of sweeps, and the waves that exceed one round of the machine are the short ones.  Bins: 64 / n_mix sweep bins per task.
-__device__ __forceinline__ int regroup_bin_mixed(int sweeps, int bin_width, int cls, int w) { return cls * w + (w - 1 - min(sweeps / bin_width, w - 1)); }
-__global__ __launch_bounds__(256) void rex_regroup_mixed_count_kernel(int n, int bin_width, MixRegions mr, const int32_t* __restrict__ cls,
-                                                                      const int32_t* __restrict__ sweeps, int32_t* __restrict__ counts,
-                                                                      unsigned* __restrict__ done) {
-  __shared__ int hist[64];
-  __shared__ bool last;
-  const int t = threadIdx.x, b = blockIdx.x, nb = gridDim.x;
-  if (t < 64) hist[t] = 0;
-  __syncthreads();
-  for (int k = t; k < REX_REGROUP_CHUNK; k += 256) {
-    const int i = b * REX_REGROUP_CHUNK + k;
-    if (i < n) atomicAdd(&hist[regroup_bin_mixed(sweeps[i], bin_width, cls[i], mr.bins_per_task)], 1);
-  }
-  __syncthreads();
-  if (t < 64) counts[b * 64 + t] = hist[t];
-  __threadfence();
-  __syncthreads();
-  if (t == 0) last = atomicAdd(done, 1u) == (unsigned)nb - 1u;
-  __syncthreads();
-  if (!last) return;
-  __threadfence();
-  __shared__ int total[64], first[64];
-  if (t < 64) { int acc = 0; for (int k = 0; k < nb; ++k) acc += counts[k * 64 + t]; total[t] = acc; }
-  __syncthreads();
   if (t == 0) {
-    for (int c = 0; c < mr.n_mix; ++c) {   // a task's bins fill its own region from its first slot
-      int acc = mr.base[c];
-      for (int k = 0; k < mr.bins_per_task; ++k) { first[c * mr.bins_per_task + k] = acc; acc += total[c * mr.bins_per_task + k]; }
+    for (int c = 0; c < key.n_classes; ++c) {
+      int acc = key.base[c];
+      for (int k = 0; k < key.bins_per_class; ++k) { first[c * key.bins_per_class + k] = acc; acc += total[c * key.bins_per_class + k]; }
     }
     *done = 0u;
   }
   __syncthreads();
-  if (t < mr.n_mix * mr.bins_per_task) { int acc = first[t]; for (int k = 0; k < nb; ++k) { const int c = counts[k * 64 + t]; counts[k * 64 + t] = acc; acc += c; } }
+  if (t < key.n_classes * key.bins_per_class) { int acc = first[t]; for (int k = 0; k < nb; ++k) { const int c = counts[k * 64 + t]; counts[k * 64 + t] = acc; acc += c; } }
 }
-__global__ __launch_bounds__(256) void rex_regroup_mixed_scatter_kernel(int n, int bin_width, MixRegions mr, const int32_t* __restrict__ cls,
-                                                                        const int32_t* __restrict__ sweeps, const int32_t* __restrict__ counts,
-                                                                        int32_t* __restrict__ slot_env) {
+__global__ __launch_bounds__(256) void rex_regroup_scatter_kernel(int n, RegroupKey key, const int32_t* __restrict__ sweeps, const int32_t* __restrict__ counts,
+                                                                  int32_t* __restrict__ out) {
   __shared__ int cursor[64];
   const int t = threadIdx.x, b = blockIdx.x;
   if (t < 64) cursor[t] = counts[b * 64 + t];
   __syncthreads();
   for (int k = t; k < REX_REGROUP_CHUNK; k += 256) {
     const int i = b * REX_REGROUP_CHUNK + k;
-    if (i < n) slot_env[atomicAdd(&cursor[regroup_bin_mixed(sweeps[i], bin_width, cls[i], mr.bins_per_task)], 1)] = i;
+    if (i < n) out[atomicAdd(&cursor[regroup_bin(key, sweeps[i], i)], 1)] = i;
   }
 }
-__global__ void rex_iota_kernel(int n, int32_t* __restrict__ perm, int32_t* __restrict__ sweeps) {
+__global__ void rex_iota_kernel(int n, int32_t* __restrict__ perm) {   // a regrouped single-task batch starts in index order
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) { perm[i] = i; sweeps[i] = 0; }
+  if (i < n) perm[i] = i;
 }
 
 // ---- controller-only kernels ----
@@ -407,83 +360,38 @@ static int validate(const RexConfig* c) {
 }
 
 // a snapshot record: the state words, and behind all records the observation rings the reset motion leaves behind
+static bool has_latency(const RexConfig& c) { return c.pd_latency > 0.0f || c.control_latency > 0.0f; }   // the sim keeps observation rings
 static size_t snapshot_floats(const RexSim* s, int nrec) {
-  const bool ring = s->cfg.pd_latency > 0.0f || s->cfg.control_latency > 0.0f;
-  return (size_t)nrec * ((size_t)s->words + (ring ? (size_t)REX_HISTORY_LEN * (size_t)s->dev.hist_words : 0));
+  return (size_t)nrec * ((size_t)s->words + (has_latency(s->cfg) ? (size_t)REX_HISTORY_LEN * (size_t)s->dev.hist_words : 0));
 }
 
-// ---- REX_TASK_MIXED: the task-sorted slot map ----
-// An env of a mixed batch keeps the task drawn for it (rex::mixed_task_of: one Philox block keyed by the seed and the global
-// env index) for its whole life, so which envs share a wave is decided ONCE: the envs are cut into chunks of neighbouring
-// indices (their state words share 64-byte sectors), a chunk's envs are sorted by task, every task's run is padded to whole
-// waves, and the chunks' workgroups are dealt to the XCDs (workgroup b runs on XCD b % 8) so that one L2 fetches a chunk's
-// sectors.  The step kernel then runs waves of ONE task: action_repeat, sweep cap, action box and reward weight are
-// wave-uniform, a 5-substep wave does not sit through gallop's sixth substep, and the kernel is the single-task kernel.
-static void host_philox4x32(uint32_t* c, uint32_t k0, uint32_t k1) {   // rex::philox4x32 on the host
-  for (int r = 0; r < 10; ++r) {
-    const uint64_t p0 = (uint64_t)0xD2511F53u * c[0], p1 = (uint64_t)0xCD9E8D57u * c[2];
-    const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c[1] ^ k0, n1 = (uint32_t)p1, n2 = (uint32_t)(p0 >> 32) ^ c[3] ^ k1, n3 = (uint32_t)p0;
-    c[0] = n0; c[1] = n1; c[2] = n2; c[3] = n3;
-    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-  }
+// ---- regrouping: the buffers and the two launches of the per-step sort (rex_regroup_*_kernel) ----
+static int regroup_chunks(const RexSim* s) { return (s->cfg.num_envs + REX_REGROUP_CHUNK - 1) / REX_REGROUP_CHUNK; }
+// The per-env sweep counts and the sort's [chunks][64] counts + completion counter, zeroed on the caller's stream: ordered ahead of
+// the first rex_regroup_count_kernel also when that stream is non-blocking (the hipStreamSynchronize at the end of rex_create covers
+// it).  The key: the task slots of the mix as classes -- one class of 64 bins for a single task; the caller of a mixed batch adds the
+// classes' regions (base) and the class array.  (rex_destroy frees whatever was allocated: RexSim starts zeroed.)
+static hipError_t regroup_alloc(RexSim* s, void* stream) {
+  const size_t n = (size_t)s->cfg.num_envs, counts = (size_t)regroup_chunks(s) * 64 + 1;
+  const int bins = 64 / s->dev.n_mix;
+  s->regroup_key.bin_width = (s->dev.max_repeat * s->dev.max_iterations + bins - 1) / bins;
+  s->regroup_key.bins_per_class = bins; s->regroup_key.n_classes = s->dev.n_mix;
+  hipError_t e = hipMalloc(&s->d_sweeps, sizeof(int32_t) * n);
+  if (e == hipSuccess) e = hipMemsetAsync(s->d_sweeps, 0, sizeof(int32_t) * n, (hipStream_t)stream);
+  if (e == hipSuccess) e = hipMalloc(&s->d_regroup, sizeof(int32_t) * counts);
+  if (e == hipSuccess) e = hipMemsetAsync(s->d_regroup, 0, sizeof(int32_t) * counts, (hipStream_t)stream);
+  if (e == hipSuccess) s->dev.sweeps = s->d_sweeps;
+  return e;
 }
-static int host_mixed_task_of(const rex::DevCfg& d, int gidx) {      // rex::mixed_task_of on the host
-  uint32_t ctr[4] = {0xFFFFFFFFu, (uint32_t)gidx, 2u, 0u};
-  host_philox4x32(ctr, d.seed_lo, d.seed_hi);
-  return d.mix_task[ctr[0] % (uint32_t)d.n_mix];
-}
-// slots[blk * epw + k] = env of wave slot k of workgroup blk (-1: padding), tasks[blk] = the workgroup's task
-// returns the number of workgroups that hold envs (the others leave at once)
-static int task_slot_map(const rex::DevCfg& d, int epw, std::vector<int32_t>& slots, std::vector<int32_t>& tasks) {
-  const int n = d.n;
-  // 8 m chunks of whole sectors (m per XCD), each at most 64 waves' worth: padding <= (epw - 1) slots per task and chunk
-  const int m = (n + 8 * 64 * epw - 1) / (8 * 64 * epw);
-  const int chunk = ((n + 8 * m - 1) / (8 * m) + 15) / 16 * 16;
-  const int nchunks = (n + chunk - 1) / chunk;
-  std::vector<std::vector<int32_t>> xs(8), xt(8);    // per XCD: its workgroups' slots and tasks
-  for (int c = 0; c < nchunks; ++c) {
-    std::vector<int32_t>& s = xs[c & 7];
-    for (int k = 0; k < d.n_mix; ++k) {
-      const size_t before = s.size();
-      for (int i = c * chunk; i < n && i < (c + 1) * chunk; ++i)
-        if (host_mixed_task_of(d, d.env_index_base + i) == d.mix_task[k]) s.push_back(i);
-      while ((s.size() - before) % (size_t)epw) s.push_back(-1);
-      for (size_t b = before / epw; b < s.size() / epw; ++b) xt[c & 7].push_back(d.mix_task[k]);
-    }
-  }
-  size_t rounds = 0, busy = 0;
-  for (int x = 0; x < 8; ++x) { busy += xt[x].size(); if (xt[x].size() > rounds) rounds = xt[x].size(); }
-  slots.assign(rounds * 8 * (size_t)epw, -1);
-  tasks.assign(rounds * 8, d.mix_task[0]);
-  for (int x = 0; x < 8; ++x)
-    for (size_t j = 0; j < xt[x].size(); ++j) {
-      const size_t b = 8 * j + (size_t)x;
-      tasks[b] = xt[x][j];
-      for (int k = 0; k < epw; ++k) slots[b * epw + k] = xs[x][j * epw + k];
-    }
-  while (!tasks.empty() && slots[(tasks.size() - 1) * epw] < 0) { tasks.pop_back(); slots.resize(tasks.size() * epw); }   // trailing padding workgroups
-  return (int)busy;
-}
-
-// The layout a regrouped mixed batch starts from (and keeps the shape of): task slot k's envs in index order in ONE region of
-// whole waves per task, regions in the order of the mix; cls[i] = task slot of env i, base[k] = first slot of region k.
-static void task_region_map(const rex::DevCfg& d, int epw, std::vector<int32_t>& slots, std::vector<int32_t>& tasks, std::vector<int32_t>& cls,
-                            int32_t base[5]) {
-  cls.resize((size_t)d.n);
-  for (int i = 0; i < d.n; ++i) {
-    const int t = host_mixed_task_of(d, d.env_index_base + i);
-    int k = 0;
-    for (int j = 1; j < d.n_mix; ++j) if (d.mix_task[j] == t) k = j;
-    cls[i] = k;
-  }
-  slots.clear(); tasks.clear();
-  for (int k = 0; k < 5; ++k) base[k] = 0;
-  for (int k = 0; k < d.n_mix; ++k) {
-    base[k] = (int32_t)slots.size();
-    for (int i = 0; i < d.n; ++i) if (cls[i] == k) slots.push_back(i);
-    while (slots.size() % (size_t)epw) slots.push_back(-1);
-    while (tasks.size() < slots.size() / epw) tasks.push_back(d.mix_task[k]);
-  }
+// next step's grouping from this step's sweep counts (stream-ordered behind the step): a single-task batch sorts its wave slots
+// (d_perm), a mixed batch every task's region of the slot map
+static void regroup_launch(RexSim* s, hipStream_t st) {
+  if (!s->d_regroup) return;
+  const int n = s->cfg.num_envs, chunks = regroup_chunks(s);
+  unsigned* done = reinterpret_cast<unsigned*>(s->d_regroup + (size_t)chunks * 64);
+  int32_t* out = s->d_perm ? s->d_perm : s->d_slot_env;
+  hipLaunchKernelGGL(rex::rex_regroup_count_kernel, dim3(chunks), dim3(256), 0, st, n, s->regroup_key, s->d_sweeps, s->d_regroup, done);
+  hipLaunchKernelGGL(rex::rex_regroup_scatter_kernel, dim3(chunks), dim3(256), 0, st, n, s->regroup_key, s->d_sweeps, s->d_regroup, out);
 }
 
 int rex_create(const RexConfig* cfg, int device, float* d_state, void* stream, RexSim** out) {
@@ -527,7 +435,7 @@ int rex_create(const RexConfig* cfg, int device, float* d_state, void* stream, R
     d.iterations = d.max_iterations = 60;
   }
   d.trace = nullptr;
-  d.slot_env = nullptr; d.block_task = nullptr; s->d_slot_env = nullptr; s->d_block_task = nullptr; s->mixed_blocks = 0; s->d_class = nullptr;
+  d.slot_env = nullptr; d.block_task = nullptr;
   d.mass_lo = cfg->mass_scale_lo; d.mass_hi = cfg->mass_scale_hi; d.mu_lo = cfg->friction_lo; d.mu_hi = cfg->friction_hi;
   s->words = rex_state_words(cfg);
   d.pose_index = cfg->pose_index; d.pose_value = cfg->pose_value;
@@ -535,7 +443,7 @@ int rex_create(const RexConfig* cfg, int device, float* d_state, void* stream, R
   d.terrain = nullptr; d.terrain_mid = nullptr; d.n_terrain = 0; d.body_params = nullptr;
   s->mot.params = nullptr; s->mot.on = 0; s->mot.per_motor = 1;
   for (int k = 0; k < 5; ++k) { s->mot.lo[k] = 0.0f; s->mot.hi[k] = 0.0f; }
-  d.perm = nullptr; d.sweeps = nullptr; s->d_perm = nullptr; s->d_sweeps = nullptr; s->d_regroup = nullptr; d.clock = nullptr; s->d_clock = nullptr; s->h_clock = nullptr;
+  d.perm = nullptr; d.sweeps = nullptr; d.clock = nullptr; s->d_clock = nullptr; s->h_clock = nullptr;
   d.geo = rex::HfGeom{256, 20.0f, 20.0f, 127.5f, 127.5f, 254.999f, 254.999f}; d.hf_stride = 65536;   /* model/terrain.py:32-54 */
   d.init_z = cfg->init_height > 0.0f ? cfg->init_height : rex::kInitZ;
   d.anchor = 0.0f;
@@ -575,18 +483,16 @@ int rex_create(const RexConfig* cfg, int device, float* d_state, void* stream, R
     const bool want = (ov ? atoi(ov) != 0 : cfg->num_envs >= 262144) && cfg->task != REX_TASK_MIXED;   // (a mixed batch is placed by its task-sorted slot map)
     if (want) {
       hipError_t e2 = hipMalloc(&s->d_perm, sizeof(int32_t) * (size_t)cfg->num_envs);
-      if (e2 == hipSuccess) e2 = hipMalloc(&s->d_sweeps, sizeof(int32_t) * (size_t)cfg->num_envs);
-      const int chunks = (cfg->num_envs + REX_REGROUP_CHUNK - 1) / REX_REGROUP_CHUNK;
-      if (e2 == hipSuccess) e2 = hipMalloc(&s->d_regroup, sizeof(int32_t) * ((size_t)chunks * 64 + 1));
-      if (e2 == hipSuccess) e2 = hipMemsetAsync(s->d_regroup, 0, sizeof(int32_t) * ((size_t)chunks * 64 + 1), (hipStream_t)stream);
-      if (e2 != hipSuccess) { (void)rex_destroy(s); return fail(REX_ENOMEM, "hipMalloc(regroup): %s", hipGetErrorString(e2)); }   // (rex_destroy frees whatever was allocated: RexSim starts zeroed)
-      hipLaunchKernelGGL(rex::rex_iota_kernel, dim3((cfg->num_envs + 255) / 256), dim3(256), 0, (hipStream_t)stream, cfg->num_envs, s->d_perm, s->d_sweeps);
-      d.perm = s->d_perm; d.sweeps = s->d_sweeps;
+      if (e2 == hipSuccess) e2 = regroup_alloc(s, stream);
+      if (e2 != hipSuccess) { (void)rex_destroy(s); return fail(REX_ENOMEM, "hipMalloc(regroup): %s", hipGetErrorString(e2)); }
+      hipLaunchKernelGGL(rex::rex_iota_kernel, dim3((cfg->num_envs + 255) / 256), dim3(256), 0, (hipStream_t)stream, cfg->num_envs, s->d_perm);
+      d.perm = s->d_perm;
     }
   }
   if (cfg->task == REX_TASK_MIXED) {
     std::vector<int32_t> slots, tasks;
-    int busy = task_slot_map(d, s->epw, slots, tasks);
+    const std::vector<int32_t> cls = rex::mixed_classes(d.n, d.env_index_base, d.seed_lo, d.seed_hi, d.n_mix);   // every env's task slot, drawn once
+    int busy = rex::task_slot_map(cls, d.n_mix, d.mix_task, s->epw, slots, tasks);
     // up to one workgroup per SIMD (MI355X: 256 CUs x 4 = 1 024) the launch is one wave per SIMD; the padding of the map must not
     // push it into a second round
     int cus = 256;
@@ -597,28 +503,20 @@ int rex_create(const RexConfig* cfg, int device, float* d_state, void* stream, R
     //  one round of the machine this library is written for, MI355X's 1 024 SIMDs, whatever partition or device it runs on; the device's own
     //  CU count only enters the regrouping decision below, which leaves results unchanged)
     const int one_round_mi355x = 1024;
-    while (!pinned && s->epw < 16 && busy > one_round_mi355x) { s->epw *= 2; busy = task_slot_map(d, s->epw, slots, tasks); }
+    while (!pinned && s->epw < 16 && busy > one_round_mi355x) { s->epw *= 2; busy = rex::task_slot_map(cls, d.n_mix, d.mix_task, s->epw, slots, tasks); }
     // More workgroups than the machine holds at once (one wave per SIMD): the batch is regrouped by sweep counts every
     // step (REX_REGROUP=0 / 1 overrides) -- regions of whole waves per task, sorted inside.  Measured at 16 384 mark-arm envs,
     // 16 envs per wave: the padding of the chunked map is a second round of full-length waves; sorted, the late waves are the short ones.
     const char* ov = getenv("REX_REGROUP");
     const bool regroup = ov ? atoi(ov) != 0 : busy > one_round;
-    std::vector<int32_t> cls;
-    if (regroup) task_region_map(d, s->epw, slots, tasks, cls, s->mix_regions.base);
+    if (regroup) rex::task_region_map(cls, d.n_mix, d.mix_task, s->epw, slots, tasks, s->regroup_key.base);
     s->mixed_blocks = (int)tasks.size();
     hipError_t e2 = hipMalloc(&s->d_slot_env, sizeof(int32_t) * slots.size());
     if (regroup) {
-      const int chunks = (cfg->num_envs + REX_REGROUP_CHUNK - 1) / REX_REGROUP_CHUNK;
-      s->mix_regions.n_mix = d.n_mix; s->mix_regions.bins_per_task = 64 / d.n_mix;
       if (e2 == hipSuccess) e2 = hipMalloc(&s->d_class, sizeof(int32_t) * cls.size());
-      if (e2 == hipSuccess) e2 = hipMemcpy(s->d_class, cls.data(), sizeof(int32_t) * cls.size(), hipMemcpyHostToDevice);
-      if (e2 == hipSuccess) e2 = hipMalloc(&s->d_sweeps, sizeof(int32_t) * (size_t)cfg->num_envs);
-      if (e2 == hipSuccess) e2 = hipMemsetAsync(s->d_sweeps, 0, sizeof(int32_t) * (size_t)cfg->num_envs, (hipStream_t)stream);   // (on the caller's stream, like the
-      //  single-task path: ordered ahead of the first rex_regroup_mixed_count_kernel also when that stream is non-blocking; the
-      //  hipStreamSynchronize at the end of rex_create covers them.  The hipMemcpy calls below block until the data is on the device.)
-      if (e2 == hipSuccess) e2 = hipMalloc(&s->d_regroup, sizeof(int32_t) * ((size_t)chunks * 64 + 1));
-      if (e2 == hipSuccess) e2 = hipMemsetAsync(s->d_regroup, 0, sizeof(int32_t) * ((size_t)chunks * 64 + 1), (hipStream_t)stream);
-      d.sweeps = s->d_sweeps;
+      if (e2 == hipSuccess) e2 = hipMemcpy(s->d_class, cls.data(), sizeof(int32_t) * cls.size(), hipMemcpyHostToDevice);   // (the hipMemcpy calls block until the data is on the device)
+      if (e2 == hipSuccess) e2 = regroup_alloc(s, stream);
+      s->regroup_key.cls = s->d_class;
     }
     if (e2 == hipSuccess) e2 = hipMalloc(&s->d_block_task, sizeof(int32_t) * tasks.size());
     if (e2 == hipSuccess) e2 = hipMemcpy(s->d_slot_env, slots.data(), sizeof(int32_t) * slots.size(), hipMemcpyHostToDevice);
@@ -690,7 +588,7 @@ int rex_set_history(RexSim* s, float* d_history) {
   if (!s) return fail(REX_EINVAL, "rex_set_history: null sim%s", "");
   // without a latency the delayed observation IS the newest one (rex.py:744-745): the ring is not needed, and the
   // snapshot holds none to restore from
-  s->dev.hist = (s->cfg.pd_latency > 0.0f || s->cfg.control_latency > 0.0f) ? d_history : nullptr;
+  s->dev.hist = has_latency(s->cfg) ? d_history : nullptr;
   return REX_OK;
 }
 
@@ -774,7 +672,7 @@ int rex_destroy(RexSim* s) {
 
 int rex_reset(RexSim* s, const int32_t* d_indices, int n, float* d_obs, void* stream) {
   if (!s) return fail(REX_EINVAL, "rex_reset: null sim%s", "");
-  if ((s->cfg.pd_latency > 0.0f || s->cfg.control_latency > 0.0f) && !s->dev.hist)
+  if (has_latency(s->cfg) && !s->dev.hist)
     return fail(REX_EINVAL, "rex_reset: pd_latency/control_latency are set but rex_set_history() was not called%s", "");
   const int count = d_indices ? n : s->cfg.num_envs;
   if (count <= 0) return d_indices ? REX_OK : fail(REX_EINVAL, "rex_reset: empty%s", "");
@@ -967,23 +865,7 @@ static int step_launch(RexSim* s, int num_steps, const float* d_action, float* d
   HIPCHK(hipGetLastError());
   // (the timed span is the step kernel's: the regrouping launches below are not part of it)
   if (s->timing == 1 || s->timing == 2) { HIPCHK(hipEventRecord(e1, st)); s->have_timing = 1; if (s->timing == 2) s->timed_steps++; }
-  if (s->d_class) {   // a regrouped mixed batch: every task's region sorted by this step's sweep counts for the next step
-    const int n = s->cfg.num_envs, width = (s->dev.max_repeat * s->dev.max_iterations + s->mix_regions.bins_per_task - 1) / s->mix_regions.bins_per_task;
-    const int chunks = (n + REX_REGROUP_CHUNK - 1) / REX_REGROUP_CHUNK;
-    unsigned* done = reinterpret_cast<unsigned*>(s->d_regroup + (size_t)chunks * 64);
-    hipLaunchKernelGGL(rex::rex_regroup_mixed_count_kernel, dim3(chunks), dim3(256), 0, st, n, width, s->mix_regions, s->d_class, s->d_sweeps, s->d_regroup, done);
-    hipLaunchKernelGGL(rex::rex_regroup_mixed_scatter_kernel, dim3(chunks), dim3(256), 0, st, n, width, s->mix_regions, s->d_class, s->d_sweeps, s->d_regroup, s->d_slot_env);
-  }
-  if (s->d_perm) {   // next step's grouping from this step's sweep counts (stream-ordered behind the step)
-    const int n = s->cfg.num_envs, width = (s->dev.max_repeat * s->dev.max_iterations + 63) / 64;
-    const int chunks = (n + REX_REGROUP_CHUNK - 1) / REX_REGROUP_CHUNK;
-    if (chunks <= 4) hipLaunchKernelGGL(rex::rex_regroup_kernel, dim3(1), dim3(1024), 0, st, n, width, s->d_sweeps, s->d_perm);
-    else {
-      unsigned* done = reinterpret_cast<unsigned*>(s->d_regroup + (size_t)chunks * 64);
-      hipLaunchKernelGGL(rex::rex_regroup_count_kernel, dim3(chunks), dim3(256), 0, st, n, width, s->d_sweeps, s->d_regroup, done);
-      hipLaunchKernelGGL(rex::rex_regroup_scatter_kernel, dim3(chunks), dim3(256), 0, st, n, width, s->d_sweeps, s->d_regroup, s->d_perm);
-    }
-  }
+  regroup_launch(s, st);
   return REX_OK;
 }
 
@@ -991,14 +873,13 @@ int rex_mixed_slot_map(const RexConfig* cfg, int envs_per_wave, int32_t* slots, 
   if (validate(cfg)) return REX_EINVAL;
   if (cfg->task != REX_TASK_MIXED || (envs_per_wave != 4 && envs_per_wave != 8 && envs_per_wave != 16))
     return fail(REX_EINVAL, "rex_mixed_slot_map: a REX_TASK_MIXED config and 4, 8 or 16 envs per wave%s", "");
-  rex::DevCfg d;
-  memset(&d, 0, sizeof d);
-  d.n = cfg->num_envs; d.env_index_base = cfg->env_index_base; d.seed_lo = (uint32_t)cfg->seed; d.seed_hi = (uint32_t)(cfg->seed >> 32);
   int ts[5];
-  d.n_mix = mix_tasks(cfg, ts);
-  for (int k = 0; k < 5; ++k) d.mix_task[k] = ts[k < d.n_mix ? k : 0];
+  const int n_mix = mix_tasks(cfg, ts);
+  int32_t mix_task[5];
+  for (int k = 0; k < 5; ++k) mix_task[k] = ts[k < n_mix ? k : 0];
   std::vector<int32_t> sl, tk;
-  task_slot_map(d, envs_per_wave, sl, tk);
+  rex::task_slot_map(rex::mixed_classes(cfg->num_envs, cfg->env_index_base, (uint32_t)cfg->seed, (uint32_t)(cfg->seed >> 32), n_mix), n_mix, mix_task,
+                     envs_per_wave, sl, tk);
   if (slots && tasks) {
     if ((int)tk.size() > max_blocks) return fail(REX_EINVAL, "rex_mixed_slot_map: buffers too small%s", "");
     memcpy(slots, sl.data(), sizeof(int32_t) * sl.size());

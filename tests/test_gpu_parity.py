@@ -1570,10 +1570,10 @@ def test_link_box_rows_change_nothing_while_no_box_touches_the_ground(torch):
     a.close(); b.close()
 
 
-@pytest.mark.parametrize("n", [3000, 9000, 70000])    # the one-workgroup sort (<= 4 096 envs) and the many-workgroup one (9 and 69 chunks, ragged last chunk)
+@pytest.mark.parametrize("n", [1025, 3000, 9000, 70000])    # chunks of the count / scatter pair: 2 (one env in the last: the smallest cross-workgroup prefix), 3, 9 and 69, ragged last chunk
 def test_regrouped_batch_is_bit_identical(torch, monkeypatch, n):
-    """REX_REGROUP=1: envs are regrouped into waves by the solver sweeps of the previous step; the wave slot -> env
-    permutation changes every step, an env's results must not."""
+    """REX_REGROUP=1: envs are regrouped into waves by the solver sweeps of the previous step (rex_regroup_count_kernel /
+    rex_regroup_scatter_kernel, one class); the wave slot -> env permutation changes every step, an env's results must not."""
     from rex_gym_amd import RexBatchEnv
     outs = {}
     for flag in ("0", "1"):
@@ -1597,7 +1597,7 @@ def test_regrouped_batch_is_bit_identical(torch, monkeypatch, n):
 @pytest.mark.parametrize("n,epw,mark", [(700, 4, "arm"), (5000, 16, "arm"), (3000, 8, "base"), (5000, 8, "arm")])    # one chunk of the count / scatter pair and several, ragged; both marks
 def test_regrouped_mixed_batch_is_bit_identical(torch, monkeypatch, n, epw, mark):
     """A REX_TASK_MIXED batch under REX_REGROUP=1: every task owns a static region of whole waves of the slot map and is
-    sorted inside it by the solver sweeps of the previous step (rex_regroup_mixed_*); against the chunked static map
+    sorted inside it by the solver sweeps of the previous step (the same two kernels, one class per task); against the chunked static map
     (REX_REGROUP=0) the waves change every step, an env's results must not -- through falls, in-launch resets and the
     per-reset mass / friction draws."""
     from rex_gym_amd import RexMixedBatchEnv

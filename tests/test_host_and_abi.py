@@ -304,3 +304,23 @@ def test_mixed_batch_slot_map_places_every_env_once_in_waves_of_one_task(L, n, e
         envs = grid[b][grid[b] >= 0]
         if envs.size:
             assert (envs[0] // chunk) % 8 == b % 8
+
+
+def test_placement_header_stands_alone_under_the_sanitizers(tmp_path):
+    """csrc/rex_placement.h (the chunked slot map, the region map of a regrouped batch and the class draw both start from) is plain
+    host code: tests/placement_main.cpp includes nothing else, is compiled here by the host C++ compiler with the address and
+    undefined-behaviour sanitizers and run as a child process; it asserts the properties of both maps for the slot-map test's cases
+    (and a two-task and a one-task mix) and the Philox known answers.  Nothing is loaded into this process."""
+    import shutil
+    import subprocess
+    cxx = next(([c] for c in ("c++", "g++") if shutil.which(c)), None)
+    if cxx is None:
+        hipcc = shutil.which("hipcc") or ("/opt/rocm/bin/hipcc" if os.path.exists("/opt/rocm/bin/hipcc") else None)
+        if hipcc is None:
+            pytest.skip("no host C++ compiler")
+        cxx = [hipcc, "-x", "c++"]
+    exe = str(tmp_path / "placement_main")
+    subprocess.run(cxx + ["-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-I", os.path.join(ROOT, "rex_gym_amd", "csrc"),
+                          os.path.join(ROOT, "tests", "placement_main.cpp"), "-o", exe], check=True)
+    run = subprocess.run([exe], capture_output=True, text=True)
+    assert run.returncode == 0, run.stdout + run.stderr
