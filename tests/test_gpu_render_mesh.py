@@ -13,7 +13,8 @@ import shutil
 import numpy as np
 import pytest
 
-from test_gpu_render import AMBIENT, CHECK_A, CHECK_B, DIFFUSE, FAR, LIGHT, NEAR, SKY, _interior, _steps, fk, rays
+import test_gpu_render as col
+from test_gpu_render import CAMERAS, _interior, _steps, camera_rays, fk, full_camera, ground_shade
 
 pytestmark = pytest.mark.gpu
 
@@ -35,17 +36,16 @@ def data_path(tmp_path_factory):
     return str(out)
 
 
-def _u8(c):
-    return np.minimum(np.floor(255.0 * c + 0.5), 255.0).astype(np.uint8)
-
-
-def brute_cast(state, env, arm, W, H, data_path):
-    """(rgb uint8 [H, W, 3], depth float64 [H, W], segment int [H, W]) of env `env`, every triangle against every ray."""
+def brute_cast(state, env, arm, W, H, data_path, field=None, camera=None, info=None):
+    """(rgb uint8 [H, W, 3], depth float64 [H, W], segment int [H, W]) of env `env`, every triangle against every ray; the
+    ground, the far plane and the shading are the collision reference's (ground_shade, whose facts `info` receives)."""
     import torch
     from rex_gym_amd import meshes
     tab = meshes.visual_table()
+    cam = full_camera(camera)
+    near, far = cam["near_plane"], cam["far_plane"]
     Rs, Os = fk(state, env, arm)
-    eye, d = rays(Os[0], W, H)
+    eye, d = camera_rays(Os[0], W, H, cam)
     dev = torch.device("cuda")
     D = torch.as_tensor(d, dtype=torch.float64, device=dev)
     E = torch.as_tensor(eye, dtype=torch.float64, device=dev)
@@ -77,7 +77,7 @@ def brute_cast(state, env, arm, W, H, data_path):
             q = torch.cross(s, a1, dim=-1)
             v = (D @ q.T) * inv
             tt = (a2 * q).sum(-1)[None] * inv
-            ok = (det != 0) & (u >= 0) & (u <= 1) & (v >= 0) & (u + v <= 1) & (tt >= NEAR)
+            ok = (det != 0) & (u >= 0) & (u <= 1) & (v >= 0) & (u + v <= 1) & (tt >= near)
             tt = torch.where(ok, tt, torch.full_like(tt, float("inf")))
             tmin, arg = tt.min(1)
             better = tmin < best
@@ -88,41 +88,40 @@ def brute_cast(state, env, arm, W, H, data_path):
                 seg = torch.where(better, torch.full_like(seg, 1 + int(b)), seg)
                 alb = torch.where(better[:, None], torch.as_tensor(tab.rgb[k], device=dev), alb)
     best, nrm, seg, alb = best.cpu().numpy(), nrm.cpu().numpy(), seg.cpu().numpy(), alb.cpu().numpy()
-    with np.errstate(divide="ignore", invalid="ignore"):
-        tpl = np.where(d[:, 2] < 0, -eye[2] / d[:, 2], np.inf)
-    ground = (tpl >= NEAR) & (tpl < best)
-    best = np.where(ground, tpl, best)
-    seg = np.where(ground, 0, seg)
-    hx, hy = eye[0] + best * d[:, 0], eye[1] + best * d[:, 1]
-    with np.errstate(invalid="ignore"):
-        chk = ((np.floor(np.where(ground, hx, 0)).astype(np.int64) + np.floor(np.where(ground, hy, 0)).astype(np.int64)) & 1) == 0
-    alb = np.where(ground[:, None], np.where(chk[:, None], CHECK_A, CHECK_B), alb)
-    nrm = np.where(ground[:, None], [0.0, 0.0, 1.0], nrm)
     nrm = nrm / np.maximum(np.linalg.norm(nrm, axis=1, keepdims=True), 1e-300)
-    nrm = np.where(((nrm * d).sum(1) > 0)[:, None], -nrm, nrm)
-    lam = AMBIENT + DIFFUSE * np.maximum(0.0, nrm @ LIGHT)
-    hit = best <= FAR
-    col = np.where(hit[:, None], alb * lam[:, None], SKY)
-    return (_u8(col).reshape(H, W, 3), np.where(hit, best, FAR).reshape(H, W), np.where(hit, seg, -1).reshape(H, W))
+    rgb, best, ground, hit, g = ground_shade(eye, d, best, nrm, alb, field, near, far)
+    seg = np.where(ground, 0, seg)
+    if info is not None:
+        info.update({k: v.reshape(H, W) for k, v in g.items()})
+    return (rgb.reshape(H, W, 3), np.where(hit, best, far).reshape(H, W), np.where(hit, seg, -1).reshape(H, W))
 
 
-def compare(env, ids, W, H, data_path):
+def compare(env, ids, W, H, data_path, field_of=None, camera=None):
     import torch
-    rgb, extra = env.render(env_ids=ids, width=W, height=H, depth=True, segmentation=True, geometry="visual")
+    rgb, extra = env.render(env_ids=ids, width=W, height=H, depth=True, segmentation=True, geometry="visual", camera=camera)
     torch.cuda.synchronize()
     rgb, dep, seg = rgb.cpu().numpy(), extra["depth"].cpu().numpy(), extra["segmentation"].cpu().numpy()
     state = env.state.cpu().numpy()
+    skies = []          # per row: the sky pixels whose depth was held to the far plane
     for k, e in enumerate(ids):
-        nrgb, ndep, nseg = brute_cast(state, e, env.mark == "arm", W, H, data_path)
+        info = {}
+        nrgb, ndep, nseg = brute_cast(state, e, env.mark == "arm", W, H, data_path, field_of(e) if field_of else None, camera, info)
         inner = _interior(nseg)
+        if field_of:    # on a heightfield: not the pixels no float32 caster can be held to (ground_shade: grazing facets, nearer
+            inner &= ~info["amb"]                         # ties); without one the mask is empty
         assert inner.mean() > 0.5
         assert (seg[k][inner] == nseg[inner]).mean() >= 0.995, (e, W, H, int((seg[k][inner] != nseg[inner]).sum()))
         both = inner & (seg[k] == nseg) & (nseg >= 0)
         err = np.abs(dep[k].astype(np.float64) - ndep)
         assert np.all(err[both] <= 1e-4), (e, W, H, float(err[both].max()))
+        sky = inner & (seg[k] < 0) & (nseg < 0)          # nothing within the far plane: the depth is the far plane
+        assert np.all(dep[k][sky] == np.float32(full_camera(camera)["far_plane"])), (e, W, H)
         drgb = np.abs(rgb[k].astype(int) - nrgb.astype(int)).max(-1)
-        assert (drgb[inner] <= 1).mean() >= 0.99, (e, W, H, float((drgb[inner] <= 1).mean()))
+        flat = inner & ~info["amb_rgb"]                  # (a facet edge switches the normal, not the depth)
+        assert (drgb[flat] <= 1).mean() >= 0.99, (e, W, H, float((drgb[flat] <= 1).mean()))
         assert (nseg > 0).sum() >= 10 and (seg[k] > 0).sum() >= 10   # the robot is in the picture
+        skies.append(int(sky.sum()))
+    return skies
 
 
 # ---------------------------------------------------------------- a. against the brute-force caster
@@ -366,3 +365,45 @@ def test_policy_player_video_meshes(tmp_path, data_path):
                         "--max-steps", "20", "--video", gif, "--video-meshes", data_path])
     im = Image.open(gif)
     assert im.n_frames == 20 and im.size == (480, 360)
+
+
+# ---------------------------------------------------------------- g. cameras other than the default (tests/test_gpu_render.py, h)
+@pytest.mark.parametrize("name,W,H", [("quadrant", 64, 48), ("near_far", 64, 48), ("down", 64, 48), ("default", 63, 47)])
+def test_cameras_on_the_plane(name, W, H, plane_meshes, data_path):
+    """the traversal order of the BVH, the instance box rejection and the two-sided triangle test under other ray directions"""
+    skies = compare(plane_meshes, [0, 3], W, H, data_path, camera=CAMERAS[name])
+    assert name != "near_far" or min(skies) >= 0.2 * W * H      # the far plane's depth is compared
+
+
+@pytest.fixture(scope="module")
+def plane_meshes(data_path):
+    env = col.plane_batch("base")
+    env.load_visual_meshes(data_path)
+    yield env
+    env.close()
+
+
+# ---------------------------------------------------------------- h. the caller-supplied heightfield pool (test_gpu_render.py, i)
+@pytest.fixture(scope="module")
+def field_meshes(data_path):
+    env, _, field_of = col.custom_field_scene()
+    env.load_visual_meshes(data_path)
+    yield env, field_of
+    env.close()
+
+
+@pytest.mark.parametrize("name", ["default", "quadrant"])
+def test_custom_heightfield(name, field_meshes, data_path):
+    """the mesh kernel's ground against the reference's (the same rays at the same fields as the collision suite casts)"""
+    env, field_of = field_meshes
+    compare(env, [0, 1, 2, 3], 64, 48, data_path, field_of=field_of, camera=CAMERAS[name])
+
+
+# ---------------------------------------------------------------- i. the store paths (test_gpu_render.py, j)
+def test_vector_stores_equal_scalar_stores(plane_meshes):
+    col.check_vector_stores_equal_scalar_stores(plane_meshes, "rex_render_visual")
+
+
+@pytest.mark.parametrize("W,H", [(61, 47), (64, 48)])
+def test_nothing_outside_the_images(plane_meshes, W, H):
+    col.check_nothing_outside_the_images(plane_meshes, "rex_render_visual", W, H, True, True)
