@@ -492,6 +492,40 @@ REX_API int rex_render_set_visuals(RexSim* sim, const float* nodes, int num_node
 REX_API int rex_render_visual(RexSim* sim, const RexCamera* cam, const int32_t* d_env_ids, int n, int width, int height,
                               uint8_t* d_rgb, float* d_depth, int16_t* d_seg, void* stream);
 
+/* Onboard sensors (csrc/rex_sense.h): what the robot perceives of the ground around it, for n envs in one launch each.
+ *
+ * A depth sensor rigidly mounted on the BASE body.  pos: the eye in the base frame [m].  fwd / up: the optical axis and the
+ * image's up direction as unit vectors in the base frame, orthogonal to each other; right = fwd x up.  Pixel (px, py), row 0 the
+ * top: ray = fwd + sx right + sy up, sx = (2 (px + .5) / W - 1) tan(fov/2) W / H, sy = (1 - 2 (py + .5) / H) tan(fov/2)  --
+ * rex_render's pixel_ray, with the axes turned by the base's rotation: the value written is the eye-space distance along the
+ * optical axis [m] of the first hit in [near_plane, far_plane], far_plane where there is none (rex_render's d_depth). */
+typedef struct RexDepthSensor {
+  float pos[3], fwd[3], up[3];
+  float fov_deg, near_plane, far_plane;   /* vertical field of view */
+  int32_t width, height;
+  int32_t see_robot;                      /* 1: the robot's own collision primitives (rex_render_gen.h) occlude; 0: ground only */
+} RexDepthSensor;
+/* The robot walks towards body -x: the eye just in front of the front face, pos (-0.18, 0, 0), looking along -x pitched 30
+ * degrees down (fwd (-cos 30, 0, -sin 30), up (-sin 30, 0, cos 30)), fov 60, near 0.02, far 10, 32 x 24, see_robot 1. */
+REX_API int rex_default_depth_sensor(RexDepthSensor* s);
+/* Row k of d_depth (float32 [n][height][width], row 0 of an image the top) is what the sensor of env d_env_ids[k] sees
+ * (int32 device array of state indices, kept in [0, num_envs) by the caller: they are not clamped; NULL: envs 0 .. n - 1, n <=
+ * num_envs), over the z = 0 plane and the heightfield of the env's current episode.  One launch on `stream`, no host sync;
+ * reads the state, the terrain pool and the heightfield, writes only d_depth.  REX_EINVAL (message in rex_last_error) without a
+ * launch for a null s or d_depth, n < 1, width or height outside 1..1024, n * width * height >= 2^29, fov_deg outside (0, 180),
+ * near_plane <= 0, far_plane <= near_plane, a non-finite field, | |fwd| - 1 |, | |up| - 1 | or |fwd . up| above 1e-3, or
+ * see_robot other than 0 or 1. */
+REX_API int rex_sense_depth(RexSim* sim, const RexDepthSensor* s, const int32_t* d_env_ids /* NULL: all envs in order */, int n,
+                            float* d_depth /* [n][height][width] */, void* stream);
+/* Ground height at K points given in the base's YAW frame (x, y [m]: world = base_xy + Rz(yaw) p, yaw = atan2(R10, R00) of the
+ * base rotation, 0 when both vanish).  relative = 0: the ground's world z (the contact code's ground_query: the facet's height
+ * over the z = 0 plane, 0 on the plane; and 0 beside the grid's footprint, where the renderer draws the plane too);  relative =
+ * 1: base z minus that.  d_points: float32 device array.  Env ids, launch
+ * and reads as rex_sense_depth; writes only d_out.  REX_EINVAL without a launch for a null d_points or d_out, n < 1, K outside
+ * 1..4096, n * K >= 2^31, or relative other than 0 or 1. */
+REX_API int rex_height_scan(RexSim* sim, const float* d_points /* [K][2] */, int K, int relative, const int32_t* d_env_ids, int n,
+                            float* d_out /* [n][K] */, void* stream);
+
 /* ---- the fused PPO learner (csrc/rex_learner.h): the losses of the reference's KL-penalty PPO (agents/ppo/algorithm.py:289-301,
  * 376-434) and their parameter gradients for a ForwardGaussianPolicy network (networks.py:69-112: obs_dim -> hidden1 -> hidden2 ->
  * out_dim, two ReLU layers), one pass over the episode memory per call.  Stateless: no RexSim, the library allocates nothing -- the

@@ -72,6 +72,13 @@ class RexCamera(ctypes.Structure):
                 ("fov_deg", ctypes.c_float), ("near_plane", ctypes.c_float), ("far_plane", ctypes.c_float)]
 
 
+class RexDepthSensor(ctypes.Structure):
+    """Mirror of `struct RexDepthSensor` (include/rexsim.h): a depth camera mounted on the base (vectors in the base frame)."""
+    _fields_ = [("pos", ctypes.c_float * 3), ("fwd", ctypes.c_float * 3), ("up", ctypes.c_float * 3),
+                ("fov_deg", ctypes.c_float), ("near_plane", ctypes.c_float), ("far_plane", ctypes.c_float),
+                ("width", ctypes.c_int32), ("height", ctypes.c_int32), ("see_robot", ctypes.c_int32)]
+
+
 class RexPpoNet(ctypes.Structure):
     """Mirror of `struct RexPpoNet` (include/rexsim.h): a two-layer ReLU network of the fused learner, torch layout."""
     _fields_ = [("obs_dim", ctypes.c_int32), ("out_dim", ctypes.c_int32), ("hidden1", ctypes.c_int32), ("hidden2", ctypes.c_int32),
@@ -162,6 +169,11 @@ _SIGS = {
                                 ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p], ctypes.c_int),
     "rex_render_visual": ([ctypes.c_void_p, ctypes.POINTER(RexCamera), ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                            ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p], ctypes.c_int),
+    "rex_default_depth_sensor": ([ctypes.POINTER(RexDepthSensor)], ctypes.c_int),
+    "rex_sense_depth": ([ctypes.c_void_p, ctypes.POINTER(RexDepthSensor), ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p],
+                        ctypes.c_int),
+    "rex_height_scan": ([ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
+                         ctypes.c_void_p], ctypes.c_int),
     "rex_ppo_workspace_bytes": ([ctypes.c_int] * 6, ctypes.c_longlong),
     "rex_ppo_returns": ([ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_float, ctypes.c_void_p, ctypes.c_void_p,
                          ctypes.c_float, ctypes.c_void_p, ctypes.c_void_p], ctypes.c_int),

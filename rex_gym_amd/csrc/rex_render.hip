@@ -22,72 +22,6 @@ struct RPrim {
   int seg, kind;
 };
 
-// nearest hit t >= near of the ray (o, d) in a primitive's local frame; returns false if none.  n: local normal at the hit
-// (not yet turned towards the eye).  Inside a primitive (the near plane cuts it) the exit is the hit, as a rasteriser
-// clipped by the near plane would show it.
-__device__ __forceinline__ bool hit_box(const float* o, const float* d, const float* h, float tnear, float& t, float* n) {
-  float t0 = -INFINITY, t1 = INFINITY;
-  int a0 = 0, a1 = 0;
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    const float inv = 1.0f / d[k];
-    float ta = (-h[k] - o[k]) * inv, tb = (h[k] - o[k]) * inv;
-    if (ta > tb) { const float x = ta; ta = tb; tb = x; }
-    if (ta > t0) { t0 = ta; a0 = k; }
-    if (tb < t1) { t1 = tb; a1 = k; }
-  }
-  if (!(t0 <= t1)) return false;
-  int a;
-  float sgn;
-  if (t0 >= tnear) { t = t0; a = a0; sgn = d[a0] > 0.0f ? -1.0f : 1.0f; }
-  else if (t1 >= tnear) { t = t1; a = a1; sgn = d[a1] > 0.0f ? 1.0f : -1.0f; }
-  else return false;
-  n[0] = a == 0 ? sgn : 0.0f; n[1] = a == 1 ? sgn : 0.0f; n[2] = a == 2 ? sgn : 0.0f;
-  return true;
-}
-
-// cylinder about the local z axis: radius h[0], half length h[2], flat caps
-__device__ __forceinline__ bool hit_cyl(const float* o, const float* d, const float* h, float tnear, float& t, float* n) {
-  const float r = h[0], hz = h[2];
-  float best = INFINITY;
-  int which = -1;   // 0 side, 1 cap
-  const float a = d[0] * d[0] + d[1] * d[1];
-  if (a > 0.0f) {
-    // closest approach of the ray to the axis first, then the two roots about it (no cancellation in b^2 - 4ac)
-    const float tc = -(o[0] * d[0] + o[1] * d[1]) / a;
-    const float px = o[0] + tc * d[0], py = o[1] + tc * d[1];
-    const float q = r * r - (px * px + py * py);
-    if (q >= 0.0f) {
-      const float dt = sqrtf(q / a);
-#pragma unroll
-      for (int s = 0; s < 2; ++s) {
-        const float ts = s == 0 ? tc - dt : tc + dt;
-        const float z = o[2] + ts * d[2];
-        if (ts >= tnear && ts < best && fabsf(z) <= hz) { best = ts; which = 0; }
-      }
-    }
-  }
-  if (d[2] != 0.0f) {
-#pragma unroll
-    for (int s = 0; s < 2; ++s) {
-      const float zc = s == 0 ? -hz : hz;
-      const float ts = (zc - o[2]) / d[2];
-      const float x = o[0] + ts * d[0], y = o[1] + ts * d[1];
-      if (ts >= tnear && ts < best && x * x + y * y <= r * r) { best = ts; which = 1 + s; }
-    }
-  }
-  if (which < 0) return false;
-  t = best;
-  if (which == 0) {
-    const float x = o[0] + t * d[0], y = o[1] + t * d[1];
-    const float inv = 1.0f / sqrtf(x * x + y * y);
-    n[0] = x * inv; n[1] = y * inv; n[2] = 0.0f;
-  } else {
-    n[0] = 0.0f; n[1] = 0.0f; n[2] = which == 1 ? -1.0f : 1.0f;
-  }
-  return true;
-}
-
 template <bool ARM>
 __global__ void __launch_bounds__(kRenderThreads) rex_render_kernel(DevCfg c, const float* __restrict__ state, RenderCam cam,
                                                                     const int32_t* __restrict__ ids, int W, int H, int vec,
@@ -192,3 +126,6 @@ hipError_t rex_launch_render(const RexSim* s, const rex::RenderCam& cam, const i
                        width, height, vec, d_rgb, d_depth, d_seg);
   return hipGetLastError();
 }
+
+// the onboard sensors (rex_sense_depth, rex_height_scan): compiled into this object, next to the functions they share with the renderer
+#include "rex_sense.hip"

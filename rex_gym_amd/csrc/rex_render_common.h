@@ -1,7 +1,8 @@
 // rex_render_common.h -- the parts of the two render kernels that must agree (rex_render.hip: collision geometry;
-// rex_render_mesh.hip: visual meshes): forward kinematics from the SoA state, the camera ray of a pixel, the ground plane /
-// checker / heightfield, sky and Lambert shading, and the whole-dword image stores.  Both kernels include it, so the ground
-// and sky pixels of the two pictures come from the same code.
+// rex_render_mesh.hip: visual meshes): forward kinematics from the SoA state, the camera ray of a pixel, the ray tests of the
+// collision primitives, the ground plane / checker / heightfield, sky and Lambert shading, and the whole-dword image stores.
+// Both kernels include it, so the ground and sky pixels of the two pictures come from the same code; the depth sensor
+// (rex_sense.hip) casts its rays with the same functions.
 #pragma once
 #include "rex_kernels.h"
 #include "rex_render.h"
@@ -33,50 +34,58 @@ __device__ __forceinline__ void axis_rot(int k, float a, float* R) {
   R[3 * i2 + i1] = s; R[3 * i2 + i2] = c;
 }
 
-// forward kinematics of env `env` (one thread): world rotation s_R[b] (row-major) and origin s_o[b] of every body b, and the
-// eye of the follow camera in s_eye
-template <bool ARM>
-__device__ __forceinline__ void render_fk(const float* __restrict__ state, int n, int env, const RenderCam& cam, float (*s_R)[9],
-                                          float (*s_o)[3], float* s_eye) {
-  // base pose: position, quaternion x y z w
+// forward kinematics from the SoA state, body by body: world rotation s_R[b] (row-major) and origin s_o[b].  A body needs its
+// parent's entry; the four leg chains (bodies 1 + 3 l .. 3 + 3 l) and the arm's chain hang off the base and off nothing else.
+// base pose: position, quaternion x y z w
+__device__ __forceinline__ void fk_base(const float* __restrict__ state, int n, int env, float* R0, float* o0) {
   const float px = ldw(state, n, REX_S_POS, env), py = ldw(state, n, REX_S_POS + 1, env), pz = ldw(state, n, REX_S_POS + 2, env);
   const float qx = ldw(state, n, REX_S_QUAT, env), qy = ldw(state, n, REX_S_QUAT + 1, env);
   const float qz = ldw(state, n, REX_S_QUAT + 2, env), qw = ldw(state, n, REX_S_QUAT + 3, env);
-  float* R0 = s_R[0];
   R0[0] = 1.0f - 2.0f * (qy * qy + qz * qz); R0[1] = 2.0f * (qx * qy - qz * qw); R0[2] = 2.0f * (qx * qz + qy * qw);
   R0[3] = 2.0f * (qx * qy + qz * qw); R0[4] = 1.0f - 2.0f * (qx * qx + qz * qz); R0[5] = 2.0f * (qy * qz - qx * qw);
   R0[6] = 2.0f * (qx * qz - qy * qw); R0[7] = 2.0f * (qy * qz + qx * qw); R0[8] = 1.0f - 2.0f * (qx * qx + qy * qy);
-  s_o[0][0] = px; s_o[0][1] = py; s_o[0][2] = pz;
-  s_eye[0] = px + cam.off[0]; s_eye[1] = py + cam.off[1]; s_eye[2] = pz + cam.off[2];
-  // legs: body b hangs off REX_PARENT[b] through joint b - 1 (joint frames carry no fixed rotation)
-  for (int b = 1; b < REX_NB; ++b) {
-    const int p = REX_PARENT[b], j = b - 1;
-    const float* Rp = s_R[p];
-    float Rq[9];
-    axis_rot(REX_JOINT_AXIS[j], ldw(state, n, REX_S_Q + j, env), Rq);
-    mat_mul(Rp, Rq, s_R[b]);
+  o0[0] = px; o0[1] = py; o0[2] = pz;
+}
+
+// legs: body b hangs off REX_PARENT[b] through joint b - 1 (joint frames carry no fixed rotation)
+__device__ __forceinline__ void fk_leg_body(const float* __restrict__ state, int n, int env, int b, float (*s_R)[9], float (*s_o)[3]) {
+  const int p = REX_PARENT[b], j = b - 1;
+  const float* Rp = s_R[p];
+  float Rq[9];
+  axis_rot(REX_JOINT_AXIS[j], ldw(state, n, REX_S_Q + j, env), Rq);
+  mat_mul(Rp, Rq, s_R[b]);
 #pragma unroll
-    for (int k = 0; k < 3; ++k)
-      s_o[b][k] = s_o[p][k] + Rp[3 * k] * (float)REX_JOINT_POS[j][0] + Rp[3 * k + 1] * (float)REX_JOINT_POS[j][1] +
-                  Rp[3 * k + 2] * (float)REX_JOINT_POS[j][2];
-  }
-  // arm: body 13 + k hangs off REXA_PARENT[k]: joint frame at REXA_POS[k] with fixed rotation REXA_E0[k], turning about
-  // REXA_AXIS_SIGN[k] * z by motor 12 + k
+  for (int k = 0; k < 3; ++k)
+    s_o[b][k] = s_o[p][k] + Rp[3 * k] * (float)REX_JOINT_POS[j][0] + Rp[3 * k + 1] * (float)REX_JOINT_POS[j][1] +
+                Rp[3 * k + 2] * (float)REX_JOINT_POS[j][2];
+}
+
+// arm: body 13 + k hangs off REXA_PARENT[k]: joint frame at REXA_POS[k] with fixed rotation REXA_E0[k], turning about
+// REXA_AXIS_SIGN[k] * z by motor 12 + k
+__device__ __forceinline__ void fk_arm_body(const float* __restrict__ state, int n, int env, int k, float (*s_R)[9], float (*s_o)[3]) {
+  const int b = REX_NB + k, p = REXA_PARENT[k];
+  const float* Rp = s_R[p];
+  float E[9], J[9], Rq[9];
+#pragma unroll
+  for (int e = 0; e < 9; ++e) E[e] = (float)REXA_E0[k][e];
+  mat_mul(Rp, E, J);
+  axis_rot(2, (float)REXA_AXIS_SIGN[k] * ldw(state, n, REX_S_Q + 12 + k, env), Rq);
+  mat_mul(J, Rq, s_R[b]);
+#pragma unroll
+  for (int e = 0; e < 3; ++e)
+    s_o[b][e] = s_o[p][e] + Rp[3 * e] * (float)REXA_POS[k][0] + Rp[3 * e + 1] * (float)REXA_POS[k][1] +
+                Rp[3 * e + 2] * (float)REXA_POS[k][2];
+}
+
+// forward kinematics of env `env` (one thread): every body b, and the eye of the follow camera in s_eye
+template <bool ARM>
+__device__ __forceinline__ void render_fk(const float* __restrict__ state, int n, int env, const RenderCam& cam, float (*s_R)[9],
+                                          float (*s_o)[3], float* s_eye) {
+  fk_base(state, n, env, s_R[0], s_o[0]);
+  s_eye[0] = s_o[0][0] + cam.off[0]; s_eye[1] = s_o[0][1] + cam.off[1]; s_eye[2] = s_o[0][2] + cam.off[2];
+  for (int b = 1; b < REX_NB; ++b) fk_leg_body(state, n, env, b, s_R, s_o);
   if (ARM) {
-    for (int k = 0; k < (ARM ? REXA_NJ : 0); ++k) {
-      const int b = REX_NB + k, p = REXA_PARENT[k];
-      const float* Rp = s_R[p];
-      float E[9], J[9], Rq[9];
-#pragma unroll
-      for (int e = 0; e < 9; ++e) E[e] = (float)REXA_E0[k][e];
-      mat_mul(Rp, E, J);
-      axis_rot(2, (float)REXA_AXIS_SIGN[k] * ldw(state, n, REX_S_Q + 12 + k, env), Rq);
-      mat_mul(J, Rq, s_R[b]);
-#pragma unroll
-      for (int e = 0; e < 3; ++e)
-        s_o[b][e] = s_o[p][e] + Rp[3 * e] * (float)REXA_POS[k][0] + Rp[3 * e + 1] * (float)REXA_POS[k][1] +
-                    Rp[3 * e + 2] * (float)REXA_POS[k][2];
-    }
+    for (int k = 0; k < (ARM ? REXA_NJ : 0); ++k) fk_arm_body(state, n, env, k, s_R, s_o);
   }
 }
 
@@ -151,6 +160,72 @@ __device__ __forceinline__ bool hit_field(const Ground& g, int ny, const float* 
   return false;
 }
 
+// nearest hit t >= near of the ray (o, d) in a primitive's local frame; returns false if none.  n: local normal at the hit
+// (not yet turned towards the eye).  Inside a primitive (the near plane cuts it) the exit is the hit, as a rasteriser
+// clipped by the near plane would show it.
+__device__ __forceinline__ bool hit_box(const float* o, const float* d, const float* h, float tnear, float& t, float* n) {
+  float t0 = -INFINITY, t1 = INFINITY;
+  int a0 = 0, a1 = 0;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    const float inv = 1.0f / d[k];
+    float ta = (-h[k] - o[k]) * inv, tb = (h[k] - o[k]) * inv;
+    if (ta > tb) { const float x = ta; ta = tb; tb = x; }
+    if (ta > t0) { t0 = ta; a0 = k; }
+    if (tb < t1) { t1 = tb; a1 = k; }
+  }
+  if (!(t0 <= t1)) return false;
+  int a;
+  float sgn;
+  if (t0 >= tnear) { t = t0; a = a0; sgn = d[a0] > 0.0f ? -1.0f : 1.0f; }
+  else if (t1 >= tnear) { t = t1; a = a1; sgn = d[a1] > 0.0f ? 1.0f : -1.0f; }
+  else return false;
+  n[0] = a == 0 ? sgn : 0.0f; n[1] = a == 1 ? sgn : 0.0f; n[2] = a == 2 ? sgn : 0.0f;
+  return true;
+}
+
+// cylinder about the local z axis: radius h[0], half length h[2], flat caps
+__device__ __forceinline__ bool hit_cyl(const float* o, const float* d, const float* h, float tnear, float& t, float* n) {
+  const float r = h[0], hz = h[2];
+  float best = INFINITY;
+  int which = -1;   // 0 side, 1 cap
+  const float a = d[0] * d[0] + d[1] * d[1];
+  if (a > 0.0f) {
+    // closest approach of the ray to the axis first, then the two roots about it (no cancellation in b^2 - 4ac)
+    const float tc = -(o[0] * d[0] + o[1] * d[1]) / a;
+    const float px = o[0] + tc * d[0], py = o[1] + tc * d[1];
+    const float q = r * r - (px * px + py * py);
+    if (q >= 0.0f) {
+      const float dt = sqrtf(q / a);
+#pragma unroll
+      for (int s = 0; s < 2; ++s) {
+        const float ts = s == 0 ? tc - dt : tc + dt;
+        const float z = o[2] + ts * d[2];
+        if (ts >= tnear && ts < best && fabsf(z) <= hz) { best = ts; which = 0; }
+      }
+    }
+  }
+  if (d[2] != 0.0f) {
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+      const float zc = s == 0 ? -hz : hz;
+      const float ts = (zc - o[2]) / d[2];
+      const float x = o[0] + ts * d[0], y = o[1] + ts * d[1];
+      if (ts >= tnear && ts < best && x * x + y * y <= r * r) { best = ts; which = 1 + s; }
+    }
+  }
+  if (which < 0) return false;
+  t = best;
+  if (which == 0) {
+    const float x = o[0] + t * d[0], y = o[1] + t * d[1];
+    const float inv = 1.0f / sqrtf(x * x + y * y);
+    n[0] = x * inv; n[1] = y * inv; n[2] = 0.0f;
+  } else {
+    n[0] = 0.0f; n[1] = 0.0f; n[2] = which == 1 ? -1.0f : 1.0f;
+  }
+  return true;
+}
+
 __device__ __forceinline__ uint32_t to_u8(float c) { return (uint32_t)fminf(floorf(255.0f * c + 0.5f), 255.0f); }
 
 // the un-normalised ray of pixel p (row-major, row 0 = the top): its parameter t is the eye-space depth
@@ -162,13 +237,14 @@ __device__ __forceinline__ void pixel_ray(long long p, int W, int H, const Rende
   for (int r = 0; r < 3; ++r) d[r] = cam.fwd[r] + sx * cam.right[r] + sy * cam.up[r];
 }
 
-// the rest of a pixel after the robot: `best` (INFINITY if nothing), its normal bn (world, either side) and albedo alb and
-// segment bseg; the ground in front of it, then sky or shading -> packed RGB, and depth / segment where something is hit
-__device__ __forceinline__ uint32_t shade_pixel(const Ground& g, int ny, const float* eye, const float* d, const RenderCam& cam,
-                                                float best, float* bn, float* alb, int bseg, float& dep, int& sg) {
-  // ground: the z = 0 plane, and the heightfield above it
+// the ground along the ray (eye, d) in front of the robot's hit `best` (INFINITY if nothing): the z = 0 plane, and the
+// heightfield above it, bounded by the plane, the far plane and the robot's hit.  -> t of the ground's hit (INFINITY: none),
+// its normal in gn
+__device__ __forceinline__ float ground_hit(const Ground& g, int ny, const float* eye, const float* d, const RenderCam& cam, float best,
+                                            float* gn) {
   const float tplane = d[2] < 0.0f ? -eye[2] / d[2] : INFINITY;
-  float tg = INFINITY, gn[3] = {0.f, 0.f, 1.f};
+  float tg = INFINITY;
+  gn[0] = 0.f; gn[1] = 0.f; gn[2] = 1.f;
   if (tplane >= cam.near_plane) tg = tplane;
   if (g.h) {
     float tf, fn[3];
@@ -176,6 +252,15 @@ __device__ __forceinline__ uint32_t shade_pixel(const Ground& g, int ny, const f
       tg = tf; gn[0] = fn[0]; gn[1] = fn[1]; gn[2] = fn[2];
     }
   }
+  return tg;
+}
+
+// the rest of a pixel after the robot: `best` (INFINITY if nothing), its normal bn (world, either side) and albedo alb and
+// segment bseg; the ground in front of it, then sky or shading -> packed RGB, and depth / segment where something is hit
+__device__ __forceinline__ uint32_t shade_pixel(const Ground& g, int ny, const float* eye, const float* d, const RenderCam& cam,
+                                                float best, float* bn, float* alb, int bseg, float& dep, int& sg) {
+  float gn[3];
+  const float tg = ground_hit(g, ny, eye, d, cam, best, gn);
   if (tg < best) {
     best = tg; bseg = 0;
     bn[0] = gn[0]; bn[1] = gn[1]; bn[2] = gn[2];

@@ -8,6 +8,7 @@
 #include "rex_kernels.h"
 #include "rex_placement.h"
 #include "rex_render.h"
+#include "rex_sense.h"
 #include "rex_visual_gen.h"
 #include "rex_error.h"
 #include <algorithm>
@@ -1065,6 +1066,64 @@ int rex_render_visual(RexSim* s, const RexCamera* cam, const int32_t* d_env_ids,
   if (!s->d_vis) return fail(REX_EINVAL, "rex_render_visual: no visual meshes set (rex_render_set_visuals)%s", "");
   HIPCHK(hipSetDevice(s->device));
   HIPCHK(rex_launch_render_mesh(s, rc, d_env_ids, n, width, height, d_rgb, d_depth, d_seg, (hipStream_t)stream));
+  return REX_OK;
+}
+
+static_assert(sizeof(RexDepthSensor) == 60, "RexDepthSensor: 12 floats and 3 int32, no padding (rex_gym_amd/_lib.py mirrors it)");
+
+int rex_default_depth_sensor(RexDepthSensor* d) {
+  if (!d) return fail(REX_EINVAL, "rex_default_depth_sensor: null pointer%s", "");
+  const float c30 = 0.86602540378443865f, s30 = 0.5f;
+  *d = RexDepthSensor{{-0.18f, 0.0f, 0.0f}, {-c30, 0.0f, -s30}, {-s30, 0.0f, c30}, 60.0f, 0.02f, 10.0f, 32, 24, 1};
+  return REX_OK;
+}
+
+// rows of a sensor call: ids given, or envs 0 .. n - 1
+static int sense_rows(const char* who, RexSim* s, const int32_t* d_env_ids, int n) {
+  if (!s) return failf(REX_EINVAL, "%s: null sim", who);
+  if (n < 1) return failf(REX_EINVAL, "%s: n %d: at least one env", who, n);
+  if (!d_env_ids && n > s->cfg.num_envs) return failf(REX_EINVAL, "%s: n %d without env ids, the sim has %d envs", who, n, s->cfg.num_envs);
+  return REX_OK;
+}
+
+int rex_sense_depth(RexSim* s, const RexDepthSensor* d, const int32_t* d_env_ids, int n, float* d_depth, void* stream) {
+  const char* who = "rex_sense_depth";
+  if (!d || !d_depth) return failf(REX_EINVAL, "%s: null pointer", who);
+  const int rows_err = sense_rows(who, s, d_env_ids, n);
+  if (rows_err != REX_OK) return rows_err;
+  if (d->width < 1 || d->width > 1024 || d->height < 1 || d->height > 1024 || (long long)n * d->width * d->height >= (1ll << 29))
+    return failf(REX_EINVAL, "%s: bad image batch (n %d, %d x %d: sides 1..1024, n * w * h < 2^29)", who, n, d->width, d->height);
+  const float* f = d->pos;   // pos, fwd, up, fov_deg, near_plane, far_plane: 12 consecutive floats
+  for (int k = 0; k < 12; ++k)
+    if (!std::isfinite(f[k])) return failf(REX_EINVAL, "%s: a non-finite field", who);
+  if (!(d->fov_deg > 0.0f) || !(d->fov_deg < 180.0f) || !(d->near_plane > 0.0f) || !(d->far_plane > d->near_plane))
+    return failf(REX_EINVAL, "%s: fov must lie in (0, 180), the near plane be positive and far > near", who);
+  if (d->see_robot != 0 && d->see_robot != 1) return failf(REX_EINVAL, "%s: see_robot must be 0 or 1", who);
+  const double fw[3] = {d->fwd[0], d->fwd[1], d->fwd[2]}, up[3] = {d->up[0], d->up[1], d->up[2]};
+  const double nf = sqrt(fw[0] * fw[0] + fw[1] * fw[1] + fw[2] * fw[2]), nu = sqrt(up[0] * up[0] + up[1] * up[1] + up[2] * up[2]);
+  const double dot = fw[0] * up[0] + fw[1] * up[1] + fw[2] * up[2];
+  if (fabs(nf - 1.0) > 1e-3 || fabs(nu - 1.0) > 1e-3 || fabs(dot) > 1e-3)
+    return failf(REX_EINVAL, "%s: fwd and up must be unit vectors orthogonal to each other (|fwd| %.6f, |up| %.6f, fwd . up %.6f)", who, nf, nu, dot);
+  rex::SenseMount m;
+  const double r[3] = {fw[1] * up[2] - fw[2] * up[1], fw[2] * up[0] - fw[0] * up[2], fw[0] * up[1] - fw[1] * up[0]};
+  for (int k = 0; k < 3; ++k) { m.pos[k] = d->pos[k]; m.fwd[k] = d->fwd[k]; m.up[k] = d->up[k]; m.right[k] = (float)r[k]; }
+  const double ty = tan(0.5 * (double)d->fov_deg * (3.14159265358979323846 / 180.0));
+  m.tan_y = (float)ty; m.tan_x = (float)(ty * (double)d->width / (double)d->height);
+  m.near_plane = d->near_plane; m.far_plane = d->far_plane; m.see_robot = d->see_robot;
+  HIPCHK(hipSetDevice(s->device));
+  HIPCHK(rex_launch_sense_depth(s, m, d_env_ids, n, d->width, d->height, d_depth, (hipStream_t)stream));
+  return REX_OK;
+}
+
+int rex_height_scan(RexSim* s, const float* d_points, int K, int relative, const int32_t* d_env_ids, int n, float* d_out, void* stream) {
+  const char* who = "rex_height_scan";
+  if (!d_points || !d_out) return failf(REX_EINVAL, "%s: null pointer", who);
+  const int rows_err = sense_rows(who, s, d_env_ids, n);
+  if (rows_err != REX_OK) return rows_err;
+  if (K < 1 || K > 4096 || (long long)n * K >= (1ll << 31)) return failf(REX_EINVAL, "%s: K %d, n %d: K in 1..4096, n * K < 2^31", who, K, n);
+  if (relative != 0 && relative != 1) return failf(REX_EINVAL, "%s: relative must be 0 or 1", who);
+  HIPCHK(hipSetDevice(s->device));
+  HIPCHK(rex_launch_height_scan(s, d_points, K, relative, d_env_ids, n, d_out, (hipStream_t)stream));
   return REX_OK;
 }
 

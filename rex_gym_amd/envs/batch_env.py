@@ -503,10 +503,7 @@ class RexBatchEnv:
                     self._all_ids = torch.arange(self.num_envs, dtype=torch.int32, device=self.device)
                 ids = self._all_ids
             else:
-                host = np.asarray(env_ids.cpu() if hasattr(env_ids, "cpu") else env_ids, dtype=np.int64).reshape(-1)
-                if host.size == 0 or host.min() < 0 or host.max() >= self.num_envs:
-                    raise IndexError(f"render: env_ids must be non-empty and lie in [0, {self.num_envs})")
-                ids = torch.as_tensor(host.astype(np.int32), device=self.device)
+                ids, _ = self._row_ids(env_ids, "render")
             k = int(ids.numel())
             if k * width * height * 3 >= 2 ** 31:
                 raise ValueError("render: k * width * height * 3 must stay below 2^31 bytes")
@@ -533,6 +530,70 @@ class RexBatchEnv:
                 raise TypeError(f"render: unknown camera field {key!r}")
             setattr(cam, key, float(v))
         return cam
+
+    def _row_ids(self, env_ids, who):
+        """env_ids of render() and the sensors -> (int32 device tensor, or None for every env in order; the number of output rows)"""
+        if env_ids is None:
+            return None, self.num_envs
+        host = np.asarray(env_ids.cpu() if hasattr(env_ids, "cpu") else env_ids, dtype=np.int64).reshape(-1)
+        if host.size == 0 or host.min() < 0 or host.max() >= self.num_envs:
+            raise IndexError(f"{who}: env_ids must be non-empty and lie in [0, {self.num_envs})")
+        return self._torch.as_tensor(host.astype(np.int32), device=self.device), int(host.size)
+
+    # ---- onboard sensors (rex_gym_amd/sensors.py) ----
+    def depth_sensor(self, width=32, height=24, position=(-0.18, 0.0, 0.0), pitch_deg=-30.0, yaw_deg=0.0, roll_deg=0.0, fov_deg=60.0,
+                     near_plane=0.02, far_plane=10.0, see_robot=True, fwd=None, up=None):
+        """A depth camera mounted on the base body of every env (rex_sense_depth): `position` is the eye in the base frame, the
+        view axes come from sensors.mount_axes(pitch_deg, yaw_deg, roll_deg) (negative pitch looks down; the default sits just
+        in front of the front face and looks 30 degrees down the walking direction, body -x) or are given as unit vectors
+        fwd / up in the base frame.  fov_deg is the vertical field of view.  see_robot=False: the ground only (the plane and
+        the env's heightfield), the robot's own links do not occlude.  Returns a sensors.DepthSensor: .read(env_ids=None,
+        out=None) -> float32 [k, height, width] on the env's device and stream, no host sync.  Bad sizes, planes or axes raise
+        here, before any launch."""
+        from .. import sensors
+        if (fwd is None) != (up is None):
+            raise ValueError("depth_sensor: give both fwd and up, or neither")
+        if fwd is None:
+            fwd, up = sensors.mount_axes(pitch_deg, yaw_deg, roll_deg)
+        return sensors.DepthSensor(self, width, height, position, fwd, up, fov_deg, near_plane, far_plane, see_robot)
+
+    def height_scan(self, points, env_ids=None, relative=True, out=None):
+        """The ground's height at K points around every base (rex_height_scan): points [K, 2] (x, y in metres) in the base's
+        YAW frame -- the grid turns with the robot's heading and stays level.  relative=True: base z minus the ground's
+        height; False: the ground's world z (the heightfield facet over the plane, 0 on the plane and beside the field).
+        Returns float32 [k, K] on the env's device and stream (`out`: a tensor of that shape to fill), env_ids as in
+        render().  The points are uploaded once per distinct array; a float32 device tensor is used as it is."""
+        from .. import sensors
+        torch = self._torch
+        with self._on_stream():
+            if isinstance(points, torch.Tensor) and points.device == self.device and points.dtype == torch.float32 and points.is_contiguous():
+                pts = points
+            else:
+                host = np.ascontiguousarray(points.cpu() if hasattr(points, "cpu") else points, dtype=np.float32)
+                if host.ndim != 2 or host.shape[1] != 2 or not 1 <= host.shape[0] <= sensors.MAX_POINTS:
+                    raise ValueError(f"height_scan: points must be [K, 2] with K in 1..{sensors.MAX_POINTS}, got {host.shape}")
+                if not np.all(np.isfinite(host)):
+                    raise ValueError("height_scan: points must be finite")
+                cache = self.__dict__.setdefault("_scan_points", {})
+                key = (host.shape, host.tobytes())
+                if key not in cache:
+                    if len(cache) >= 8:
+                        cache.clear()
+                    cache[key] = torch.as_tensor(host, device=self.device)
+                pts = cache[key]
+            if pts.dim() != 2 or pts.shape[1] != 2 or not 1 <= pts.shape[0] <= sensors.MAX_POINTS:
+                raise ValueError(f"height_scan: points must be [K, 2] with K in 1..{sensors.MAX_POINTS}, got {tuple(pts.shape)}")
+            K = int(pts.shape[0])
+            ids, k = self._row_ids(env_ids, "height_scan")
+            if k * K >= 2 ** 31:
+                raise ValueError("height_scan: k * K must stay below 2^31")
+            if out is None:
+                out = torch.empty((k, K), dtype=torch.float32, device=self.device)
+            else:
+                sensors.check_out(out, (k, K), self, "height_scan")
+            _lib.check(self._L.rex_height_scan(self._h, pts.data_ptr(), K, 1 if relative else 0, ids.data_ptr() if ids is not None else None,
+                                               k, out.data_ptr(), self._stream_ptr()), "rex_height_scan")
+        return out
 
     def _action_bounds(self):
         if self._act_lo is None:
