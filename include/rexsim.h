@@ -526,6 +526,45 @@ REX_API int rex_sense_depth(RexSim* sim, const RexDepthSensor* s, const int32_t*
 REX_API int rex_height_scan(RexSim* sim, const float* d_points /* [K][2] */, int K, int relative, const int32_t* d_env_ids, int n,
                             float* d_out /* [n][K] */, void* stream);
 
+/* Body and foot kinematics (csrc/rex_kinematics.h): where every link and every foot of n envs is, how it moves, and how far each
+ * foot is from the ground -- what rewards and privileged observations are built from, in one read-only launch.
+ *
+ * NB = rex_num_bodies(cfg): 13 (mark base) or 19 (mark arm), in the body order of REX_PARENT / REXA_PARENT (csrc/rex_model_gen.h,
+ * rex_arm_model_gen.h): body 0 the base, 1 + 3 l .. 3 + 3 l the shoulder, leg and foot link of leg l (front_left, front_right,
+ * rear_left, rear_right), 13 .. 18 the arm.  Every member of RexKinematicsOut is a device array of n rows, float32 unless
+ * noted, or NULL: a null member is not computed.  World frame unless noted.
+ *   link_pos    [n][NB][3]  origin of each link frame
+ *   link_quat   [n][NB][4]  its orientation x y z w, unit norm (the sign is not fixed)
+ *   link_linvel [n][NB][3]  velocity of that origin;  link_angvel [n][NB][3]  angular velocity of the link.  REX_S_LINVEL is
+ *                           the velocity of the base link frame's origin, the point REX_S_POS is integrated with (the base's
+ *                           centre of mass lies there); the links' follow by  w_b = w_p + qd_j a_j,  v_b = v_p + w_p x (o_b - o_p)
+ *   toe_pos     [n][8][3]   the 8 contact candidates of the physics, point p = 2 leg + e for the two ends e of the toe
+ *                           cylinder: the lowest point of the end's rim along the ground normal under the end's centre (the
+ *                           centre's projection when the cylinder's axis is parallel to that normal)
+ *   toe_vel     [n][8][3]   velocity of the foot link's material point there
+ *   toe_dist    [n][8]      the signed distance the contact solver sees: (z - ground height) * normal z at the point, the
+ *                           1 mm collision margin included (on the plane: toe_pos z).  Beside a heightfield's footprint the
+ *                           ground keeps the height of the grid's border, as it does for the solver
+ *   toe_normal  [n][8][3]   the ground's unit normal at the point; (0, 0, 1) on the plane
+ *   toe_in_reach [n][8]     uint8, 1 where toe_dist < 0.02 m: the contact breaking threshold that activates the point's rows
+ *   base_body   [n][9]      base linear velocity, base angular velocity and the unit gravity direction, all in the BASE frame
+ *                           (R0^T v, R0^T w, R0^T (0, 0, -1)) */
+typedef struct RexKinematicsOut {
+  float *link_pos, *link_quat, *link_linvel, *link_angvel;
+  float *toe_pos, *toe_vel, *toe_dist, *toe_normal;
+  uint8_t* toe_in_reach;
+  float* base_body;
+} RexKinematicsOut;
+/* Number of bodies of the robot of `cfg`: 13 (mark base) or 19 (mark arm); REX_EINVAL for a null cfg. */
+REX_API int rex_num_bodies(const RexConfig* cfg);
+/* Row k of every output is env d_env_ids[k] (int32 device array of state indices, kept in [0, num_envs) by the caller; NULL: envs
+ * 0 .. n - 1, n <= num_envs).  One launch on `stream`, no host sync; reads the state, the terrain pool and the heightfield of the
+ * env's current episode, writes only the arrays of `out` (each needs the alignment of its element and no more: element stores).
+ * REX_EINVAL (message in rex_last_error) without a launch for a null
+ * sim or out, n < 1, n > num_envs without ids, n * NB * 4 >= 2^31, or an `out` whose members are all NULL. */
+REX_API int rex_kinematics(RexSim* sim, const int32_t* d_env_ids /* NULL: envs 0 .. n - 1 */, int n, const RexKinematicsOut* out,
+                           void* stream);
+
 /* ---- the fused PPO learner (csrc/rex_learner.h): the losses of the reference's KL-penalty PPO (agents/ppo/algorithm.py:289-301,
  * 376-434) and their parameter gradients for a ForwardGaussianPolicy network (networks.py:69-112: obs_dim -> hidden1 -> hidden2 ->
  * out_dim, two ReLU layers), one pass over the episode memory per call.  Stateless: no RexSim, the library allocates nothing -- the

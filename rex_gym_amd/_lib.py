@@ -79,6 +79,13 @@ class RexDepthSensor(ctypes.Structure):
                 ("width", ctypes.c_int32), ("height", ctypes.c_int32), ("see_robot", ctypes.c_int32)]
 
 
+class RexKinematicsOut(ctypes.Structure):
+    """Mirror of `struct RexKinematicsOut` (include/rexsim.h): the device arrays rex_kinematics fills (a null one is skipped)."""
+    _fields_ = [("link_pos", ctypes.c_void_p), ("link_quat", ctypes.c_void_p), ("link_linvel", ctypes.c_void_p), ("link_angvel", ctypes.c_void_p),
+                ("toe_pos", ctypes.c_void_p), ("toe_vel", ctypes.c_void_p), ("toe_dist", ctypes.c_void_p), ("toe_normal", ctypes.c_void_p),
+                ("toe_in_reach", ctypes.c_void_p), ("base_body", ctypes.c_void_p)]
+
+
 class RexPpoNet(ctypes.Structure):
     """Mirror of `struct RexPpoNet` (include/rexsim.h): a two-layer ReLU network of the fused learner, torch layout."""
     _fields_ = [("obs_dim", ctypes.c_int32), ("out_dim", ctypes.c_int32), ("hidden1", ctypes.c_int32), ("hidden2", ctypes.c_int32),
@@ -174,6 +181,8 @@ _SIGS = {
                         ctypes.c_int),
     "rex_height_scan": ([ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
                          ctypes.c_void_p], ctypes.c_int),
+    "rex_num_bodies": ([ctypes.POINTER(RexConfig)], ctypes.c_int),
+    "rex_kinematics": ([ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(RexKinematicsOut), ctypes.c_void_p], ctypes.c_int),
     "rex_ppo_workspace_bytes": ([ctypes.c_int] * 6, ctypes.c_longlong),
     "rex_ppo_returns": ([ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_float, ctypes.c_void_p, ctypes.c_void_p,
                          ctypes.c_float, ctypes.c_void_p, ctypes.c_void_p], ctypes.c_int),

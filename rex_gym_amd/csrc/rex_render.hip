@@ -129,3 +129,5 @@ hipError_t rex_launch_render(const RexSim* s, const rex::RenderCam& cam, const i
 
 // the onboard sensors (rex_sense_depth, rex_height_scan): compiled into this object, next to the functions they share with the renderer
 #include "rex_sense.hip"
+// body and foot kinematics (rex_kinematics): the same forward kinematics once more, read out instead of drawn
+#include "rex_kinematics.hip"

@@ -9,6 +9,7 @@
 #include "rex_placement.h"
 #include "rex_render.h"
 #include "rex_sense.h"
+#include "rex_kinematics.h"
 #include "rex_visual_gen.h"
 #include "rex_error.h"
 #include <algorithm>
@@ -1124,6 +1125,27 @@ int rex_height_scan(RexSim* s, const float* d_points, int K, int relative, const
   if (relative != 0 && relative != 1) return failf(REX_EINVAL, "%s: relative must be 0 or 1", who);
   HIPCHK(hipSetDevice(s->device));
   HIPCHK(rex_launch_height_scan(s, d_points, K, relative, d_env_ids, n, d_out, (hipStream_t)stream));
+  return REX_OK;
+}
+
+static_assert(sizeof(RexKinematicsOut) == 80, "RexKinematicsOut: 10 pointers, no padding (rex_gym_amd/_lib.py mirrors it)");
+
+int rex_num_bodies(const RexConfig* c) {
+  if (!c) return REX_EINVAL;
+  return c->mark == REX_MARK_ARM ? REX_NB + REXA_NJ : REX_NB;
+}
+
+int rex_kinematics(RexSim* s, const int32_t* d_env_ids, int n, const RexKinematicsOut* out, void* stream) {
+  const char* who = "rex_kinematics";
+  if (!out) return failf(REX_EINVAL, "%s: null pointer", who);
+  const int rows_err = sense_rows(who, s, d_env_ids, n);
+  if (rows_err != REX_OK) return rows_err;
+  if ((long long)n * rex_num_bodies(&s->cfg) * 4 >= (1ll << 31)) return failf(REX_EINVAL, "%s: n %d: n * bodies * 4 must stay below 2^31", who, n);
+  if (!out->link_pos && !out->link_quat && !out->link_linvel && !out->link_angvel && !out->toe_pos && !out->toe_vel && !out->toe_dist &&
+      !out->toe_normal && !out->toe_in_reach && !out->base_body)
+    return failf(REX_EINVAL, "%s: every output pointer is null", who);
+  HIPCHK(hipSetDevice(s->device));
+  HIPCHK(rex_launch_kinematics(s, d_env_ids, n, *out, (hipStream_t)stream));
   return REX_OK;
 }
 
