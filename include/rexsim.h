@@ -565,6 +565,48 @@ REX_API int rex_num_bodies(const RexConfig* cfg);
 REX_API int rex_kinematics(RexSim* sim, const int32_t* d_env_ids /* NULL: envs 0 .. n - 1 */, int n, const RexKinematicsOut* out,
                            void* stream);
 
+/* Rigid-body dynamics readout (csrc/rex_dynamics.h): the equations of motion of n envs at their current state, in one read-only
+ * launch -- what model-based controllers, torque feed-forward, momentum rewards and ground-reaction estimates are built from.
+ * Mark base only (18 degrees of freedom).
+ *
+ * The generalized velocity is v[18]: v[0:3] the world linear velocity of the base link frame's origin (REX_S_LINVEL), v[3:6] the
+ * world angular velocity of the base (REX_S_ANGVEL), v[6:18] the 12 joint rates in motor order -- the order of link_linvel /
+ * link_angvel and of the state words.  The outputs are defined by
+ *     M(q) vdot + h(q, v) = S^T tau + sum_p J_p^T f_p        (S selects v[6:18]; f_p is a world force at toe point p)
+ * Every member of RexDynamicsOut is a float32 device array of n rows, or NULL: a null member is not computed.
+ *   mass_matrix  [n][18][18]   M(q), symmetric; both triangles are written, from one value per pair; blocks that couple two
+ *                              different legs are exact zeros
+ *   bias         [n][18]       h(q, v): Coriolis, centrifugal and gyroscopic terms plus gravity at the sim's g = 10 m/s^2, on the
+ *                              left-hand side: a robot at rest has bias[0:3] = (0, 0, +mass * 10).  The sim's Bullet-style linear
+ *                              and angular damping forces are NOT part of it
+ *   gravity      [n][18]       h(q, 0)
+ *   toe_jacobian [n][8][3][18] toe_vel[p] = J_p v for point p = 2 leg + e of rex_kinematics, the foot link's material point at
+ *                              toe_pos[p]:  J_p = [ 1 | -[P - o_0]x | a_j x (P - o_j) for the three joints j of the point's leg ],
+ *                              o_0 the base origin, a_j and o_j a joint's world axis and position; the columns of the other
+ *                              three legs are written as zeros
+ *   com          [n][6]        centre of mass: world position, world velocity
+ *   momentum     [n][6]        linear momentum, then angular momentum about the centre of mass, world axes
+ *   mass         [n]           total mass with the env's scales
+ * Masses are the ones the step uses in the env's current episode: REX_MASS times the base / leg mass scale of the explicit
+ * rex_set_body_params table or of the per-reset draws of mass_scale_range.  The scales touch the masses only: every link's
+ * rotational inertia about its own centre of mass stays the model's constant, for the base as for the legs, as in the step
+ * (Bullet keeps the inertia tensors computed at load time).  The on_rack anchor is not part of the readout. */
+typedef struct RexDynamicsOut {
+  float *mass_matrix;
+  float *bias;
+  float *gravity;
+  float *toe_jacobian;
+  float *com;
+  float *momentum;
+  float *mass;
+} RexDynamicsOut;
+/* Rows, launch and reads as rex_kinematics, plus the env's mass scales; writes only the arrays of `out`.  mass_matrix and
+ * toe_jacobian are written in 16-byte chunks and must be 16-byte aligned (every row of either is a multiple of 16 bytes); the other
+ * arrays need the alignment of a float.  REX_EINVAL (message in rex_last_error) without a launch for a null sim or out, n < 1,
+ * n > num_envs without ids, n * 8 * 3 * 18 >= 2^31, an `out` whose members are all NULL, a mass_matrix or toe_jacobian that is not
+ * 16-byte aligned, or a sim of mark arm. */
+REX_API int rex_dynamics(RexSim* sim, const int32_t* d_env_ids /* NULL: envs 0 .. n - 1 */, int n, const RexDynamicsOut* out, void* stream);
+
 /* ---- the fused PPO learner (csrc/rex_learner.h): the losses of the reference's KL-penalty PPO (agents/ppo/algorithm.py:289-301,
  * 376-434) and their parameter gradients for a ForwardGaussianPolicy network (networks.py:69-112: obs_dim -> hidden1 -> hidden2 ->
  * out_dim, two ReLU layers), one pass over the episode memory per call.  Stateless: no RexSim, the library allocates nothing -- the

@@ -86,6 +86,12 @@ class RexKinematicsOut(ctypes.Structure):
                 ("toe_in_reach", ctypes.c_void_p), ("base_body", ctypes.c_void_p)]
 
 
+class RexDynamicsOut(ctypes.Structure):
+    """Mirror of `struct RexDynamicsOut` (include/rexsim.h): the device arrays rex_dynamics fills (a null one is skipped)."""
+    _fields_ = [("mass_matrix", ctypes.c_void_p), ("bias", ctypes.c_void_p), ("gravity", ctypes.c_void_p), ("toe_jacobian", ctypes.c_void_p),
+                ("com", ctypes.c_void_p), ("momentum", ctypes.c_void_p), ("mass", ctypes.c_void_p)]
+
+
 class RexPpoNet(ctypes.Structure):
     """Mirror of `struct RexPpoNet` (include/rexsim.h): a two-layer ReLU network of the fused learner, torch layout."""
     _fields_ = [("obs_dim", ctypes.c_int32), ("out_dim", ctypes.c_int32), ("hidden1", ctypes.c_int32), ("hidden2", ctypes.c_int32),
@@ -183,6 +189,7 @@ _SIGS = {
                          ctypes.c_void_p], ctypes.c_int),
     "rex_num_bodies": ([ctypes.POINTER(RexConfig)], ctypes.c_int),
     "rex_kinematics": ([ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(RexKinematicsOut), ctypes.c_void_p], ctypes.c_int),
+    "rex_dynamics": ([ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(RexDynamicsOut), ctypes.c_void_p], ctypes.c_int),
     "rex_ppo_workspace_bytes": ([ctypes.c_int] * 6, ctypes.c_longlong),
     "rex_ppo_returns": ([ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_float, ctypes.c_void_p, ctypes.c_void_p,
                          ctypes.c_float, ctypes.c_void_p, ctypes.c_void_p], ctypes.c_int),

@@ -5,10 +5,9 @@
 //      the leg-0 lane writes the base's entry, then every lane walks its leg's three bodies, and the leg-3 lane of a mark-arm env
 //      the arm's six.  Behind each body the lane derives the link's quaternion and its velocities by the recursion of
 //      rex_kinematics.h and writes the link's rows of the requested tensors; the leg-0 lane the base's and base_body.
-//   2. The two toe points of the lane's leg: the geometric front end of leg_pass's "toe contact points" block (rex_device.h),
-//      restated here from the same constants (kToeRad, kToeHalf, kBreaking, REX_TOE_Z) and the contact code's own env_ground and
-//      ground_query -- restated and not shared, so that no step kernel compiles differently.  The plane is the heightfield form
-//      with normal +z and height 0, which is the value the flat branch of leg_pass computes.
+//   2. The two toe points of the lane's leg: toe_point of rex_toe_point.h (the geometric front end of leg_pass's "toe contact
+//      points" block, restated there for this kernel and rex_dynamics.hip) over the contact code's own env_ground; in reach is
+//      dist < kBreaking.
 // Stores: every lane writes its own short pieces (3 or 4 floats of a link, 6 of a leg's two toe points) straight to the output rows.
 // Staging a workgroup's slice of each tensor in LDS and writing it out workgroup-linearly, 16 bytes per lane, was measured and was
 // slower (profiles/kinematics.md: 9.3 against 8.1 us for the full readout of 4 096 envs -- two barriers per tensor cost more than the
@@ -17,6 +16,7 @@
 // (Built as part of rex_render.hip's object, like rex_sense.hip: rex_gym_amd/build.py INCLUDED_IN.)
 #include "rex_render_common.h"
 #include "rex_kinematics.h"
+#include "rex_toe_point.h"
 
 namespace rex {
 
@@ -129,24 +129,15 @@ __global__ void __launch_bounds__(kKinThreads) rex_kinematics_kernel(DevCfg c, c
   if (out.toe_pos || out.toe_vel || out.toe_dist || out.toe_normal || out.toe_in_reach) {   // (the same in every thread)
     const int b3 = 3 + 3 * leg;
     const f3 z3 = mk(R[b3][2], R[b3][5], R[b3][8]), aw = mk(R[b3][1], R[b3][4], R[b3][7]);   // the foot link's z, the toe cylinder's axis
-    const f3 tc = op + (float)REX_TOE_Z * z3;
+    const f3 tc = toe_centre(op, z3);
     const bool field = c.n_terrain > 0;
     Ground g{};
     if (field) g = env_ground(c, env, c.env_index_base + env, (int)ldi(state, n, Lay<NM>::EPISODE, env));
 #pragma unroll
     for (int e = 0; e < 2; ++e) {
-      const float sg = e == 0 ? -kToeHalf : kToeHalf;
-      const f3 ce = tc + sg * aw;
-      f3 n0 = mk(0.f, 0.f, 1.f), nrm = mk(0.f, 0.f, 1.f);
-      float h0 = 0.0f, h = 0.0f;
-      if (field) ground_query(g, ce.x, ce.y, h0, n0);     // normal under the end centre ...
-      const float na = dot(n0, aw);
-      const f3 dv = n0 - na * aw;
-      const float dn2 = dot(dv, dv);
-      const float inv = dn2 > 1e-18f ? rsqrtf(dn2) : 0.0f;
-      const f3 P = ce - (kToeRad * inv) * dv;              // ... -> the lowest point along it ...
-      if (field) ground_query(g, P.x, P.y, h, nrm);        // ... -> the local plane
-      const float dist = (P.z - h) * nrm.z;
+      const ToePoint tp = toe_point(g, field, tc, aw, e);
+      const f3 P = tp.P, nrm = tp.nrm;
+      const float dist = tp.dist;
       if (live) {
         const size_t at = (size_t)row * 8 + 2 * leg + e;   // point p = 2 leg + e
         if (out.toe_pos) put3(out.toe_pos + 3 * at, P);

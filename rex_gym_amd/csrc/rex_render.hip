@@ -131,3 +131,5 @@ hipError_t rex_launch_render(const RexSim* s, const rex::RenderCam& cam, const i
 #include "rex_sense.hip"
 // body and foot kinematics (rex_kinematics): the same forward kinematics once more, read out instead of drawn
 #include "rex_kinematics.hip"
+// the equations of motion at that pose (rex_dynamics): mass matrix, bias forces, toe Jacobians
+#include "rex_dynamics.hip"

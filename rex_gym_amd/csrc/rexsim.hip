@@ -10,6 +10,7 @@
 #include "rex_render.h"
 #include "rex_sense.h"
 #include "rex_kinematics.h"
+#include "rex_dynamics.h"
 #include "rex_visual_gen.h"
 #include "rex_error.h"
 #include <algorithm>
@@ -1146,6 +1147,24 @@ int rex_kinematics(RexSim* s, const int32_t* d_env_ids, int n, const RexKinemati
     return failf(REX_EINVAL, "%s: every output pointer is null", who);
   HIPCHK(hipSetDevice(s->device));
   HIPCHK(rex_launch_kinematics(s, d_env_ids, n, *out, (hipStream_t)stream));
+  return REX_OK;
+}
+
+static_assert(sizeof(RexDynamicsOut) == 56, "RexDynamicsOut: 7 pointers, no padding (rex_gym_amd/_lib.py mirrors it)");
+
+int rex_dynamics(RexSim* s, const int32_t* d_env_ids, int n, const RexDynamicsOut* out, void* stream) {
+  const char* who = "rex_dynamics";
+  if (!out) return failf(REX_EINVAL, "%s: null pointer", who);
+  const int rows_err = sense_rows(who, s, d_env_ids, n);
+  if (rows_err != REX_OK) return rows_err;
+  if (s->cfg.mark == REX_MARK_ARM) return failf(REX_EINVAL, "%s: mark arm is not supported (18 degrees of freedom only)", who);
+  if ((long long)n * rex::kDynJacFloats >= (1ll << 31)) return failf(REX_EINVAL, "%s: n %d: n * 8 * 3 * 18 must stay below 2^31", who, n);
+  if (!out->mass_matrix && !out->bias && !out->gravity && !out->toe_jacobian && !out->com && !out->momentum && !out->mass)
+    return failf(REX_EINVAL, "%s: every output pointer is null", who);
+  if (((uintptr_t)out->mass_matrix | (uintptr_t)out->toe_jacobian) & 15u)   // (the kernel writes these two in 16-byte chunks)
+    return failf(REX_EINVAL, "%s: mass_matrix and toe_jacobian must be 16-byte aligned", who);
+  HIPCHK(hipSetDevice(s->device));
+  HIPCHK(rex_launch_dynamics(s, d_env_ids, n, *out, (hipStream_t)stream));
   return REX_OK;
 }
 

@@ -624,6 +624,30 @@ class RexBatchEnv:
         from .. import kinematics
         return kinematics.read(self, env_ids, fields, out)
 
+    # ---- rigid-body dynamics (rex_gym_amd/dynamics.py) ----
+    @property
+    def dof_names(self):
+        """The 18 names of the generalized velocity's components (rows and columns of dynamics()): six of the base -- world linear
+        velocity of the base origin, world angular velocity -- then the motor names in motor order, from the model tables."""
+        from .. import dynamics
+        return dynamics.dof_names()
+
+    def dynamics(self, env_ids=None, fields=None, out=None):
+        """The equations of motion at the current state (rex_dynamics), in one read-only launch on the env's device and stream, no
+        host sync:  M(q) vdot + bias(q, v) = S^T tau + sum_p J_p^T f_p  with v = (base linear velocity, base angular velocity, 12
+        joint rates), world axes (env.dof_names).  Returns a dynamics.Dynamics whose attributes are float32 tensors of k rows
+        (env_ids as in render(); default: every env, in order):
+          mass_matrix [k, 18, 18]: M(q), symmetric
+          bias [k, 18]: Coriolis, centrifugal and gyroscopic terms plus gravity (g = 10; at rest bias[0:3] = (0, 0, +mass * 10));
+              the sim's damping forces are not part of it.  gravity [k, 18]: bias at v = 0
+          toe_jacobian [k, 4, 2, 3, 18]: toe_vel = J v for the contact candidate at both ends of each toe (kinematics().toe_pos)
+          com [k, 6]: centre of mass, world position and velocity (properties com_pos, com_vel)
+          momentum [k, 6]: linear momentum, angular momentum about the centre of mass;  mass [k]: total mass
+        Masses carry the env's base / leg mass scales of the current episode; rotational inertias do not, as in the step.
+        fields, out: as in kinematics().  Mark 'arm' raises NotImplementedError.  Every argument error is raised before any launch."""
+        from .. import dynamics
+        return dynamics.read(self, env_ids, fields, out)
+
     def _action_bounds(self):
         if self._act_lo is None:
             torch = self._torch
