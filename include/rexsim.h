@@ -607,6 +607,34 @@ typedef struct RexDynamicsOut {
  * 16-byte aligned, or a sim of mark arm. */
 REX_API int rex_dynamics(RexSim* sim, const int32_t* d_env_ids /* NULL: envs 0 .. n - 1 */, int n, const RexDynamicsOut* out, void* stream);
 
+/* Solves with the mass matrix (csrc/rex_dynamics_solve.h): the equation above solved on the device, one launch, M(q) never written
+ * out -- a block elimination over its structure (the 6 x 6 base block, four 3 x 3 leg blocks that do not couple to each other,
+ * the 3 x 6 couplings).  Mark base only.  Rows, ids and launch as rex_dynamics: no host sync; v, the order of its 18 components,
+ * the masses and the toe points are rex_dynamics'.
+ *
+ *   rex_dynamics_solve    x [n][K][18] = M(q)^-1 rhs [n][K][18]: K right-hand sides per row.  d_x may be d_rhs itself (in place).
+ *                         The Delassus matrix J M^-1 J^T of the toe points is K = 24 with rhs = the rows of toe_jacobian.
+ *   rex_forward_dynamics  vdot [n][18] = M^-1 (S^T tau + sum_p J_p^T f_p + w - h(q, v)) for the load: joint torques tau [n][12],
+ *                         world forces f_p [n][8][3] at the toe points p = 2 leg + e, and a base wrench w [n][6] -- a world force
+ *                         at the base origin, then a world moment: rows 0..5 of the equation.  A NULL member is zero (all three
+ *                         NULL: free fall from the current state); the ground is queried only when toe forces are given.
+ *   rex_apply_impulse     the same load as impulses [N s, N m s]:  dv [n][18] = M^-1 (S^T j + sum_p J_p^T p_p + w), written to d_dv
+ *                         unless that is NULL, and ADDED to REX_S_LINVEL, REX_S_ANGVEL and REX_S_QD of each row's env in the
+ *                         caller-owned state (one float add per word; no other word is touched): an external push between two
+ *                         control steps.  The rows must name distinct envs -- the caller's duty, not checked here (two rows of one
+ *                         env race on its words).
+ * Like `bias`, the forward and the impulse form leave out what the step adds to the rigid-body equation: the Bullet-style damping,
+ * joint-limit rows, contact rows and the on_rack anchor.
+ * REX_EINVAL (message in rex_last_error) without a launch for: a null sim, rhs, x, vdot, load or impulse; n < 1; n > num_envs without
+ * ids; K < 1; n * K * 18 >= 2^31; d_rhs and d_x that overlap without being equal; an impulse whose three members are all NULL; a sim
+ * of mark arm; rex_apply_impulse on an on_rack sim (its base hangs on the anchor). */
+typedef struct RexDynamicsLoad { const float *joint, *toe, *base; } RexDynamicsLoad;   /* [n][12], [n][8][3], [n][6]; NULL = zero */
+REX_API int rex_dynamics_solve(RexSim* sim, const int32_t* d_env_ids /* NULL: envs 0 .. n - 1 */, int n, int K, const float* d_rhs, float* d_x,
+                               void* stream);
+REX_API int rex_forward_dynamics(RexSim* sim, const int32_t* d_env_ids, int n, const RexDynamicsLoad* load, float* d_vdot, void* stream);
+REX_API int rex_apply_impulse(RexSim* sim, const int32_t* d_env_ids, int n, const RexDynamicsLoad* impulse, float* d_dv /* nullable */,
+                              void* stream);
+
 /* ---- the fused PPO learner (csrc/rex_learner.h): the losses of the reference's KL-penalty PPO (agents/ppo/algorithm.py:289-301,
  * 376-434) and their parameter gradients for a ForwardGaussianPolicy network (networks.py:69-112: obs_dim -> hidden1 -> hidden2 ->
  * out_dim, two ReLU layers), one pass over the episode memory per call.  Stateless: no RexSim, the library allocates nothing -- the

@@ -92,6 +92,11 @@ class RexDynamicsOut(ctypes.Structure):
                 ("com", ctypes.c_void_p), ("momentum", ctypes.c_void_p), ("mass", ctypes.c_void_p)]
 
 
+class RexDynamicsLoad(ctypes.Structure):
+    """Mirror of `struct RexDynamicsLoad` (include/rexsim.h): the device arrays of a load or an impulse (a null one is zero)."""
+    _fields_ = [("joint", ctypes.c_void_p), ("toe", ctypes.c_void_p), ("base", ctypes.c_void_p)]
+
+
 class RexPpoNet(ctypes.Structure):
     """Mirror of `struct RexPpoNet` (include/rexsim.h): a two-layer ReLU network of the fused learner, torch layout."""
     _fields_ = [("obs_dim", ctypes.c_int32), ("out_dim", ctypes.c_int32), ("hidden1", ctypes.c_int32), ("hidden2", ctypes.c_int32),
@@ -190,6 +195,9 @@ _SIGS = {
     "rex_num_bodies": ([ctypes.POINTER(RexConfig)], ctypes.c_int),
     "rex_kinematics": ([ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(RexKinematicsOut), ctypes.c_void_p], ctypes.c_int),
     "rex_dynamics": ([ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(RexDynamicsOut), ctypes.c_void_p], ctypes.c_int),
+    "rex_dynamics_solve": ([ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p], ctypes.c_int),
+    "rex_forward_dynamics": ([ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(RexDynamicsLoad), ctypes.c_void_p, ctypes.c_void_p], ctypes.c_int),
+    "rex_apply_impulse": ([ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(RexDynamicsLoad), ctypes.c_void_p, ctypes.c_void_p], ctypes.c_int),
     "rex_ppo_workspace_bytes": ([ctypes.c_int] * 6, ctypes.c_longlong),
     "rex_ppo_returns": ([ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_float, ctypes.c_void_p, ctypes.c_void_p,
                          ctypes.c_float, ctypes.c_void_p, ctypes.c_void_p], ctypes.c_int),

@@ -23,20 +23,19 @@
 // against 12.1 us for the full readout of 4 096 envs), unlike at the 1 KB per env of rex_kinematics.  The small outputs (bias,
 // gravity, com, momentum, mass) are stored by the lanes that hold them.  A null output pointer is a launch-uniform skip.  Lanes
 // of rows past the end repeat the last row, take part in the barriers and the quad sums, and store nothing to global memory.
+// Sections 1 and 2 live in rex_dynamics_leg.h, which rex_dynamics_solve.hip (the solves with M) includes too.
 // (Built as part of rex_render.hip's object, like rex_kinematics.hip: rex_gym_amd/build.py INCLUDED_IN.)
 #include "rex_render_common.h"
 #include "rex_dynamics.h"
+#include "rex_dynamics_leg.h"
 #include "rex_toe_point.h"
 
 namespace rex {
 
 namespace {
 
-// floats of one env's tables R[NB][9], o[NB][3] (odd: the lanes of one leg in neighbouring envs fall on different banks)
-constexpr int kDynStride = (12 * REX_NB) | 1;
 // dynamic LDS of a workgroup: the FK tables, then over them (once every lane holds its leg in registers) the workgroup's rows of
 // M, then of J, on their way out
-constexpr int kDynFkBytes = ((kDynEnvs * kDynStride + 3) & ~3) * (int)sizeof(float);
 constexpr int kDynStageBytes = kDynEnvs * kDynJacFloats * (int)sizeof(float);
 constexpr int kDynLdsBytes = kDynStageBytes > kDynFkBytes ? kDynStageBytes : kDynFkBytes;
 static_assert(kDynLdsBytes <= 64 * 1024, "no more than the 64 KiB a launch gets by default");
@@ -49,56 +48,9 @@ __device__ __forceinline__ void flush_rows(const float* lds, float* dst, int cou
   for (int k = threadIdx.x; k < count4; k += kDynThreads) dst4[k] = src4[k];
 }
 
-// the leg's model constants are read from leg 0's entries of the tables: the four legs carry the same links
-constexpr bool dyn_legs_alike() {
-  for (int l = 1; l < REX_NLEG; ++l)
-    for (int i = 0; i < 3; ++i) {
-      const int a = 1 + i, b = 1 + 3 * l + i;
-      if (REX_MASS[a] != REX_MASS[b] || REX_JOINT_AXIS[a - 1] != REX_JOINT_AXIS[b - 1]) return false;
-      for (int k = 0; k < 3; ++k)
-        if (REX_COM[a][k] != REX_COM[b][k] || REX_INERTIA[a][k] != REX_INERTIA[b][k]) return false;
-    }
-  for (int b = 0; b < REX_NB; ++b)
-    if (REX_INERTIA[b][3] != 0.0 || REX_INERTIA[b][4] != 0.0 || REX_INERTIA[b][5] != 0.0) return false;   // principal axes = body axes
-  return REX_COM[0][0] == 0.0 && REX_COM[0][1] == 0.0 && REX_COM[0][2] == 0.0;                             // the base's centre of mass is o_0
-}
-static_assert(dyn_legs_alike(), "rex_dynamics_kernel reads leg 0's link constants for every leg, diagonal inertias, and a base whose centre of mass is its origin");
-
-__device__ __forceinline__ void dput3(float* dst, f3 v) { dst[0] = v.x; dst[1] = v.y; dst[2] = v.z; }
-__device__ __forceinline__ f3 quad_sum(f3 v) { return mk(group_sum<4>(v.x), group_sum<4>(v.y), group_sum<4>(v.z)); }
-__device__ __forceinline__ float comp(f3 v, int k) { return k == 0 ? v.x : k == 1 ? v.y : v.z; }
-
-// bias wrench of the leg's links at zero generalized acceleration: subtree sums Fs[i], Ns[i] about o_0 (i = 0: the whole leg)
-struct DynLeg {
-  f3 p[3], r[3], a[3];     // joint points and link centres of mass relative to o_0, joint axes (world)
-  s33 I[3];                // link inertias about their centres of mass, world axes
-  float m[3], qd[3];
-};
-__device__ __forceinline__ void leg_bias(const DynLeg& L, f3 w0, f3* Fs, f3* Ns) {
-  f3 w = w0, al = mk(0.f, 0.f, 0.f), ao = mk(0.f, 0.f, 0.f), pp = mk(0.f, 0.f, 0.f);
-  f3 F[3], N[3];
-#pragma unroll
-  for (int i = 0; i < 3; ++i) {
-    const f3 d = L.p[i] - pp;
-    ao = ao + cross(al, d) + cross(w, cross(w, d));          // the joint point, carried by the parent
-    al = al + L.qd[i] * cross(w, L.a[i]);                    // d/dt (qd a) at constant rate: the axis turns with the parent
-    w = w + L.qd[i] * L.a[i];
-    const f3 rc = L.r[i] - L.p[i];
-    const f3 ac = ao + cross(al, rc) + cross(w, cross(w, rc));
-    F[i] = L.m[i] * (ac + mk(0.f, 0.f, kGravity));
-    N[i] = mul(L.I[i], al) + cross(w, mul(L.I[i], w)) + cross(L.r[i], F[i]);
-    pp = L.p[i];
-  }
-  Fs[2] = F[2]; Ns[2] = N[2];
-  Fs[1] = F[1] + Fs[2]; Ns[1] = N[1] + Ns[2];
-  Fs[0] = F[0] + Fs[1]; Ns[0] = N[0] + Ns[1];
-}
-
 __global__ void __launch_bounds__(kDynThreads) rex_dynamics_kernel(DevCfg c, const float* __restrict__ state, const int32_t* __restrict__ ids,
                                                                    int rows_total, RexDynamicsOut out) {
-  constexpr int NM = REX_NUM_MOTORS;
   extern __shared__ __attribute__((aligned(16))) float s_dyn[];
-  const int n = c.n;
   const int el = threadIdx.x >> 2, leg = threadIdx.x & 3;
   const bool live = blockIdx.x * kDynEnvs + el < rows_total;
   const int row = min(blockIdx.x * kDynEnvs + el, rows_total - 1);   // (the grid has ceil(rows_total / kDynEnvs) workgroups)
@@ -107,64 +59,23 @@ __global__ void __launch_bounds__(kDynThreads) rex_dynamics_kernel(DevCfg c, con
   float (*R)[9] = reinterpret_cast<float (*)[9]>(s_dyn + el * kDynStride);
   float (*o)[3] = reinterpret_cast<float (*)[3]>(s_dyn + el * kDynStride + 9 * REX_NB);
 
-  // ---- 1. the chain of this leg ----
-  if (leg == 0) fk_base(state, n, env, R[0], o[0]);
-  __syncthreads();
-  const f3 o0 = mk(o[0][0], o[0][1], o[0][2]);
-  const f3 v0 = mk(ldw(state, n, REX_S_LINVEL, env), ldw(state, n, REX_S_LINVEL + 1, env), ldw(state, n, REX_S_LINVEL + 2, env));
-  const f3 w0 = mk(ldw(state, n, REX_S_ANGVEL, env), ldw(state, n, REX_S_ANGVEL + 1, env), ldw(state, n, REX_S_ANGVEL + 2, env));
-  const Ground g = env_ground(c, env, c.env_index_base + env, (int)ldi(state, n, Lay<NM>::EPISODE, env));
-  DynLeg L;
-  f3 ofoot = o0, z3 = mk(0.f, 0.f, 1.f), aw = mk(0.f, 1.f, 0.f);     // the foot link's origin, z axis and toe axis (its y)
-#pragma unroll
-  for (int i = 0; i < 3; ++i) {
-    const int b = 1 + 3 * leg + i, ax = REX_JOINT_AXIS[i];
-    fk_leg_body(state, n, env, b, R, o);
-    const float* Rb = R[b];
-    const f3 ex = mk(Rb[0], Rb[3], Rb[6]), ey = mk(Rb[1], Rb[4], Rb[7]), ez = mk(Rb[2], Rb[5], Rb[8]);
-    const f3 ob = mk(o[b][0], o[b][1], o[b][2]);
-    L.p[i] = ob - o0;
-    L.a[i] = ax == 0 ? ex : ax == 1 ? ey : ez;
-    L.r[i] = L.p[i] + ((float)REX_COM[1 + i][0] * ex + (float)REX_COM[1 + i][1] * ey + (float)REX_COM[1 + i][2] * ez);
-    L.I[i] = rot_inertia(ex, ey, ez, (float)REX_INERTIA[1 + i][0], (float)REX_INERTIA[1 + i][1], (float)REX_INERTIA[1 + i][2]);
-    L.m[i] = (float)REX_MASS[1 + i] * g.leg_mass_scale;
-    L.qd[i] = ldw(state, n, Lay<NM>::QD + b - 1, env);
-    if (i == 2) { ofoot = ob; z3 = ez; aw = ey; }
-  }
-  const float* R0 = R[0];
-  const f3 bx = mk(R0[0], R0[3], R0[6]), by = mk(R0[1], R0[4], R0[7]), bz = mk(R0[2], R0[5], R0[8]);
-  const s33 I0 = rot_inertia(bx, by, bz, (float)REX_INERTIA[0][0], (float)REX_INERTIA[0][1], (float)REX_INERTIA[0][2]);
-  const float m0 = (float)REX_MASS[0] * g.base_mass_scale;
-  const float base = leg == 0 ? 1.0f : 0.0f;     // the leg-0 lane carries the base body into the quad sums
-
-  // ---- 2. composites, the leg's blocks of M ----
-  float mc[3]; f3 hc[3]; s33 Ic[3];
-#pragma unroll
-  for (int i = 2; i >= 0; --i) {
-    mc[i] = L.m[i]; hc[i] = L.m[i] * L.r[i]; Ic[i] = L.I[i];
-    add_point(Ic[i], L.m[i], L.r[i]);
-    if (i < 2) { mc[i] += mc[i + 1]; hc[i] = hc[i] + hc[i + 1]; add(Ic[i], Ic[i + 1]); }
-  }
-  f3 u[3], f[3], nn[3];
-#pragma unroll
-  for (int i = 0; i < 3; ++i) {
-    u[i] = cross(L.p[i], L.a[i]);
-    f[i] = mc[i] * u[i] + cross(L.a[i], hc[i]);
-    nn[i] = mul(Ic[i], L.a[i]) + cross(hc[i], u[i]);
-  }
-  const float mt = group_sum<4>(mc[0] + base * m0);
-  const f3 ht = quad_sum(hc[0]);
-  s33 It = Ic[0];
-  It.xx += base * I0.xx; It.yy += base * I0.yy; It.zz += base * I0.zz; It.xy += base * I0.xy; It.xz += base * I0.xz; It.yz += base * I0.yz;
-  It.xx = group_sum<4>(It.xx); It.yy = group_sum<4>(It.yy); It.zz = group_sum<4>(It.zz);
-  It.xy = group_sum<4>(It.xy); It.xz = group_sum<4>(It.xz); It.yz = group_sum<4>(It.yz);
+  // ---- 1. the chain of this leg, 2. composites and the leg's blocks of M (rex_dynamics_leg.h) ----
+  DynFront F;
+  dyn_load_leg(c, state, env, leg, R, o, F);
+  DynComposite C;
+  dyn_composites(F, C);
+  const f3 o0 = F.o0, v0 = F.v0, w0 = F.w0, ofoot = F.ofoot, z3 = F.z3, aw = F.aw;
+  const Ground& g = F.g;
+  const DynLeg& L = F.L;
+  const s33& I0 = F.I0;
+  const float m0 = F.m0, base = F.base, mt = C.mt;
+  const float (&mc)[3] = C.mc; const f3 (&hc)[3] = C.hc; const f3 (&f)[3] = C.f; const f3 (&nn)[3] = C.nn;
+  const f3 ht = C.ht;
+  const s33 It = C.It;
 
   if (out.mass_matrix) {                                   // (every `if (out.x)` is the same in every thread)
     float H[3][3];
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-      for (int j = 0; j <= i; ++j) H[i][j] = H[j][i] = dot(u[j], f[i]) + dot(L.a[j], nn[i]);
+    dyn_leg_block(L, C, H);
     __syncthreads();                                       // every lane holds its leg in registers: the FK tables are dead
     {
       float* Mr = s_dyn + el * kDynMassFloats;             // the row's M in LDS (lanes past the end stage their copy of the last row)

@@ -1,0 +1,262 @@
+// rex_dynamics_solve.hip -- x = M(q)^-1 b for every env by block elimination, M never leaving the registers (rex_dynamics_solve.h).
+//
+// rex_dynamics_solve_kernel: one lane per (output row, leg), a row's four legs one DPP quad, 32 rows per workgroup -- the mapping and
+// the front end of rex_dynamics_kernel (rex_dynamics_leg.h): after it the lane holds its leg's block H_f (3 x 3, symmetric positive
+// definite), its coupling B_f (6 x 3) and, like every lane of the quad, the base block Mb.  In the order v = (base 6, leg 0, .. leg 3)
+//     M = [ Mb  B_0 .. B_3 ;  B_f^T  H_f on the diagonal, zeros between two legs ],
+// so, all in registers:
+//   1. H_f = L D L^T (3 x 3, three reciprocals).
+//   2. Y_f = H_f^-1 B_f^T (3 x 6).
+//   3. The Schur complement A = Mb - sum_f B_f Y_f: 21 entries, one group_sum<4> each; every lane of the quad holds A.
+//   4. A = G G^T (Cholesky of the 6 x 6, on every lane: redundant work, no LDS and no atomics).
+//   5. Per right-hand side b = (b_0 [6], b_f [3] per leg):  c = b_0 - sum_f Y_f^T b_f (six group sums),  x_0 = A^-1 c,
+//      x_f = H_f^-1 b_f - Y_f x_0.
+// Modes (launch-uniform, RexSolveArgs::mode):
+//   kSolveRhs      K right-hand sides per row from rhs [n][K][18] to x [n][K][18]; rhs may be x itself (a row's right-hand side k
+//                  is in the quad's registers before any of its lanes stores the solution k).
+//   kSolveForward  one right-hand side assembled here,  b = S^T tau + sum_p J_p^T f_p + w - h(q, v):  tau the lane's three joints;
+//                  f_p at the lane's own two toe points (toe_point, rex_toe_point.h: the point rex_kinematics and rex_dynamics
+//                  report; the ground is queried only when toe forces are given), the base rows of J_p^T f_p = (f, (P - o_0) x f)
+//                  by quad sum, the leg rows col_i . f with col_i = a_i x (P - o_0 - p_i);  w the wrench at the base origin;
+//                  h from leg_bias exactly as rex_dynamics' bias.  x is vdot [n][18].
+//   kSolveImpulse  the same assembly without h, every input an impulse; x is dv [n][18] (or null), and the lanes add dv to the
+//                  velocity words of the row's env -- REX_S_LINVEL by the leg-0 lane, REX_S_ANGVEL by the leg-1 lane, the leg's
+//                  three REX_S_QD words by its own lane -- one fp32 add per word from the value the front end read; no other
+//                  state word is touched.  Rows must name distinct envs (the caller's duty, include/rexsim.h).
+// What the two assembled modes leave out is stated once, in rex_dynamics_solve.h.
+// Stores: each lane stores its own 3 (or 3 + 3) floats of a solution.  Staging a workgroup's solutions in LDS and writing them
+// linearly was measured and is slower at every K (7.43 against 7.10 us at K = 1, 25.6 against 19.7 us at K = 24 for 4 096 envs,
+// profiles/dynamics_solve.md): a solution is 72 bytes a row, not the 1 296 of a row of M, and the two barriers per solution cost
+// more than the narrower stores.  Lanes of rows past the end repeat the last row, take part in the barrier and the quad sums, and
+// store nothing.
+// (Built as part of rex_render.hip's object, like rex_dynamics.hip: rex_gym_amd/build.py INCLUDED_IN.)
+#include "rex_render_common.h"
+#include "rex_dynamics_solve.h"
+#include "rex_dynamics_leg.h"
+#include "rex_toe_point.h"
+
+namespace rex {
+
+namespace {
+
+static_assert(kDynFkBytes <= 64 * 1024, "no more than the 64 KiB a launch gets by default");
+
+// H = L D L^T of a symmetric positive definite 3 x 3, the reciprocals of D kept
+struct Ldl3 { float l10, l20, l21, i0, i1, i2; };
+__device__ __forceinline__ Ldl3 ldl3(const float (&H)[3][3]) {
+  Ldl3 q;
+  q.i0 = 1.0f / H[0][0];
+  q.l10 = H[1][0] * q.i0;
+  q.l20 = H[2][0] * q.i0;
+  const float d1 = H[1][1] - q.l10 * H[1][0];
+  q.i1 = 1.0f / d1;
+  const float t21 = H[2][1] - q.l20 * H[1][0];
+  q.l21 = t21 * q.i1;
+  const float d2 = H[2][2] - q.l20 * H[2][0] - q.l21 * t21;
+  q.i2 = 1.0f / d2;
+  return q;
+}
+__device__ __forceinline__ void ldl3_solve(const Ldl3& q, float b0, float b1, float b2, float (&x)[3]) {
+  const float y1 = b1 - q.l10 * b0;
+  const float y2 = b2 - q.l20 * b0 - q.l21 * y1;
+  x[2] = y2 * q.i2;
+  x[1] = y1 * q.i1 - q.l21 * x[2];
+  x[0] = b0 * q.i0 - q.l10 * x[1] - q.l20 * x[2];
+}
+
+// A = G G^T of a symmetric positive definite 6 x 6 (lower triangle read); G's strict lower triangle and the reciprocals of its diagonal
+struct Chol6 { float g[6][6], inv[6]; };
+__device__ __forceinline__ void chol6(const float (&A)[6][6], Chol6& q) {
+#pragma unroll
+  for (int j = 0; j < 6; ++j) {
+    float s = A[j][j];
+#pragma unroll
+    for (int k = 0; k < j; ++k) s -= q.g[j][k] * q.g[j][k];
+    q.inv[j] = 1.0f / sqrtf(s);
+#pragma unroll
+    for (int i = j + 1; i < 6; ++i) {
+      float t = A[i][j];
+#pragma unroll
+      for (int k = 0; k < j; ++k) t -= q.g[i][k] * q.g[j][k];
+      q.g[i][j] = t * q.inv[j];
+    }
+  }
+}
+__device__ __forceinline__ void chol6_solve(const Chol6& q, const float (&c)[6], float (&x)[6]) {
+  float y[6];
+#pragma unroll
+  for (int i = 0; i < 6; ++i) {
+    float t = c[i];
+#pragma unroll
+    for (int k = 0; k < i; ++k) t -= q.g[i][k] * y[k];
+    y[i] = t * q.inv[i];
+  }
+#pragma unroll
+  for (int i = 5; i >= 0; --i) {
+    float t = y[i];
+#pragma unroll
+    for (int k = i + 1; k < 6; ++k) t -= q.g[k][i] * x[k];
+    x[i] = t * q.inv[i];
+  }
+}
+
+__global__ void __launch_bounds__(kDynThreads) rex_dynamics_solve_kernel(DevCfg c, const float* state, const int32_t* __restrict__ ids,
+                                                                         int rows_total, RexSolveArgs a) {
+  constexpr int NM = REX_NUM_MOTORS;
+  extern __shared__ __attribute__((aligned(16))) float s_sol[];
+  const int el = threadIdx.x >> 2, leg = threadIdx.x & 3;
+  const bool live = blockIdx.x * kDynEnvs + el < rows_total;
+  const int row = min(blockIdx.x * kDynEnvs + el, rows_total - 1);   // (the grid has ceil(rows_total / kDynEnvs) workgroups)
+  const int env = ids ? ids[row] : row;                              // the state's env index (checked on the host)
+  float (*R)[9] = reinterpret_cast<float (*)[9]>(s_sol + el * kDynStride);
+  float (*o)[3] = reinterpret_cast<float (*)[3]>(s_sol + el * kDynStride + 9 * REX_NB);
+
+  // ---- the leg, its composites, H_f and B_f, the base block (rex_dynamics_leg.h) ----
+  DynFront F;
+  dyn_load_leg(c, state, env, leg, R, o, F);
+  DynComposite C;
+  dyn_composites(F, C);
+  const DynLeg& L = F.L;
+  float H[3][3];
+  dyn_leg_block(L, C, H);
+
+  // ---- 1.-4. the factors ----
+  const Ldl3 hq = ldl3(H);
+  float Y[3][6];                                             // Y_f = H_f^-1 B_f^T: column k solves for row k of B_f
+#pragma unroll
+  for (int k = 0; k < 6; ++k) {
+    float y[3];
+    if (k < 3) ldl3_solve(hq, comp(C.f[0], k), comp(C.f[1], k), comp(C.f[2], k), y);
+    else ldl3_solve(hq, comp(C.nn[0], k - 3), comp(C.nn[1], k - 3), comp(C.nn[2], k - 3), y);
+    Y[0][k] = y[0]; Y[1][k] = y[1]; Y[2][k] = y[2];
+  }
+  const f3 ht = C.ht;
+  const s33 It = C.It;
+  const float Mb[6][6] = {{C.mt, 0.f, 0.f, 0.f, ht.z, -ht.y}, {0.f, C.mt, 0.f, -ht.z, 0.f, ht.x}, {0.f, 0.f, C.mt, ht.y, -ht.x, 0.f},
+                          {0.f, -ht.z, ht.y, It.xx, It.xy, It.xz}, {ht.z, 0.f, -ht.x, It.xy, It.yy, It.yz}, {-ht.y, ht.x, 0.f, It.xz, It.yz, It.zz}};
+  float A[6][6];
+#pragma unroll
+  for (int r = 0; r < 6; ++r)
+#pragma unroll
+    for (int k = 0; k <= r; ++k) {
+      const float br0 = r < 3 ? comp(C.f[0], r) : comp(C.nn[0], r - 3), br1 = r < 3 ? comp(C.f[1], r) : comp(C.nn[1], r - 3),
+                  br2 = r < 3 ? comp(C.f[2], r) : comp(C.nn[2], r - 3);
+      const float s = br0 * Y[0][k] + br1 * Y[1][k] + br2 * Y[2][k];
+      A[r][k] = A[k][r] = Mb[r][k] - group_sum<4>(s);
+    }
+  Chol6 aq;
+  chol6(A, aq);
+
+  // x = M^-1 (b0, bf of every leg); x0 on every lane of the quad, xf the lane's own
+  auto solve = [&](const float (&b0)[6], const float (&bf)[3], float (&x0)[6], float (&xf)[3]) {
+    float cc[6];
+#pragma unroll
+    for (int k = 0; k < 6; ++k) {
+      const float t = Y[0][k] * bf[0] + Y[1][k] * bf[1] + Y[2][k] * bf[2];
+      cc[k] = b0[k] - group_sum<4>(t);
+    }
+    chol6_solve(aq, cc, x0);
+    float hs[3];
+    ldl3_solve(hq, bf[0], bf[1], bf[2], hs);
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+      float t = hs[i];
+#pragma unroll
+      for (int k = 0; k < 6; ++k) t -= Y[i][k] * x0[k];
+      xf[i] = t;
+    }
+  };
+  // the lane's share of a solution: its leg's three joints; the base's linear part by the leg-0 lane, its angular part by the leg-1 lane
+  auto store = [&](float* d, const float (&x0)[6], const float (&xf)[3]) {
+    d[6 + 3 * leg] = xf[0]; d[7 + 3 * leg] = xf[1]; d[8 + 3 * leg] = xf[2];
+    if (leg == 0) { d[0] = x0[0]; d[1] = x0[1]; d[2] = x0[2]; }
+    else if (leg == 1) { d[3] = x0[3]; d[4] = x0[4]; d[5] = x0[5]; }
+  };
+  // a solution of every row of the workgroup to wg[row in the workgroup * stride + 0 .. 17]
+  auto emit = [&](float* wg, size_t stride, const float (&x0)[6], const float (&xf)[3]) {
+    if (live) store(wg + (size_t)el * stride, x0, xf);
+  };
+  const size_t wg_row = (size_t)blockIdx.x * kDynEnvs;       // the workgroup's first row
+
+  if (a.mode == kSolveRhs) {                                 // (a.mode and every pointer test below are the same in every thread)
+    for (int k = 0; k < a.K; ++k) {
+      const size_t at = ((size_t)row * (size_t)a.K + (size_t)k) * kDynDof;
+      const float* b = a.rhs + at;
+      const float b0[6] = {b[0], b[1], b[2], b[3], b[4], b[5]};
+      const float bf[3] = {b[6 + 3 * leg], b[7 + 3 * leg], b[8 + 3 * leg]};
+      float x0[6], xf[3];
+      solve(b0, bf, x0, xf);
+      emit(a.x + (wg_row * (size_t)a.K + (size_t)k) * kDynDof, (size_t)a.K * kDynDof, x0, xf);
+    }
+    return;
+  }
+
+  // ---- the right-hand side of a load: b = S^T tau + sum_p J_p^T f_p + w (- h) ----
+  f3 bl = mk(0.f, 0.f, 0.f), bn = mk(0.f, 0.f, 0.f);         // base rows: force, moment about o_0
+  float bf[3] = {0.f, 0.f, 0.f};
+  if (a.joint) {
+    const float* t = a.joint + (size_t)row * 12 + 3 * leg;
+    bf[0] = t[0]; bf[1] = t[1]; bf[2] = t[2];
+  }
+  if (a.toe) {
+    const f3 tc = toe_centre(F.ofoot, F.z3);
+    const bool field = c.n_terrain > 0;
+#pragma unroll
+    for (int e = 0; e < 2; ++e) {
+      const f3 d = toe_point(F.g, field, tc, F.aw, e).P - F.o0;
+      const float* fp = a.toe + ((size_t)row * 8 + 2 * leg + e) * 3;
+      const f3 fe = mk(fp[0], fp[1], fp[2]);
+      bl = bl + fe;
+      bn = bn + cross(d, fe);
+#pragma unroll
+      for (int i = 0; i < 3; ++i) bf[i] += dot(cross(L.a[i], d - L.p[i]), fe);
+    }
+    bl = quad_sum(bl); bn = quad_sum(bn);
+  }
+  if (a.base) {
+    const float* w = a.base + (size_t)row * 6;
+    bl = bl + mk(w[0], w[1], w[2]);
+    bn = bn + mk(w[3], w[4], w[5]);
+  }
+  if (a.mode == kSolveForward) {                             // h as rex_dynamics' bias
+    f3 Fs[3], Ns[3];
+    leg_bias(L, F.w0, Fs, Ns);
+    const f3 gz = mk(0.f, 0.f, kGravity);
+    const f3 Ft = quad_sum(Fs[0] + (F.base * F.m0) * gz);
+    const f3 Nt = quad_sum(Ns[0] + F.base * cross(F.w0, mul(F.I0, F.w0)));
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+      const float tq = dot(L.a[i], Ns[i] - cross(L.p[i], Fs[i]));
+      bf[i] -= tq;
+    }
+    bl = bl - Ft; bn = bn - Nt;
+  }
+  const float b0[6] = {bl.x, bl.y, bl.z, bn.x, bn.y, bn.z};
+  float x0[6], xf[3];
+  solve(b0, bf, x0, xf);
+  if (a.x) emit(a.x + wg_row * kDynDof, kDynDof, x0, xf);
+  if (a.state && live) {                                             // the push: v += dv, one add per word
+    const int n = c.n;
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+      const float v = L.qd[i] + xf[i];
+      stw(a.state, n, Lay<NM>::QD + 3 * leg + i, env, v);
+    }
+    if (leg == 0) {
+      const f3 v = F.v0 + mk(x0[0], x0[1], x0[2]);
+      stw(a.state, n, REX_S_LINVEL, env, v.x); stw(a.state, n, REX_S_LINVEL + 1, env, v.y); stw(a.state, n, REX_S_LINVEL + 2, env, v.z);
+    } else if (leg == 1) {
+      const f3 v = F.w0 + mk(x0[3], x0[4], x0[5]);
+      stw(a.state, n, REX_S_ANGVEL, env, v.x); stw(a.state, n, REX_S_ANGVEL + 1, env, v.y); stw(a.state, n, REX_S_ANGVEL + 2, env, v.z);
+    }
+  }
+}
+
+}  // namespace
+}  // namespace rex
+
+hipError_t rex_launch_dynamics_solve(const RexSim* s, const int32_t* d_ids, int n, const rex::RexSolveArgs& a, hipStream_t st) {
+  const int blocks = (n + rex::kDynEnvs - 1) / rex::kDynEnvs;
+  hipLaunchKernelGGL(rex::rex_dynamics_solve_kernel, dim3(blocks), dim3(rex::kDynThreads), rex::kDynFkBytes, st, s->dev, s->d_state, d_ids, n, a);
+  return hipGetLastError();
+}

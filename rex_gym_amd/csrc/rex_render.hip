@@ -133,3 +133,5 @@ hipError_t rex_launch_render(const RexSim* s, const rex::RenderCam& cam, const i
 #include "rex_kinematics.hip"
 // the equations of motion at that pose (rex_dynamics): mass matrix, bias forces, toe Jacobians
 #include "rex_dynamics.hip"
+// solves with that mass matrix (rex_dynamics_solve, rex_forward_dynamics, rex_apply_impulse): the same front end, M kept in registers
+#include "rex_dynamics_solve.hip"

@@ -11,6 +11,7 @@
 #include "rex_sense.h"
 #include "rex_kinematics.h"
 #include "rex_dynamics.h"
+#include "rex_dynamics_solve.h"
 #include "rex_visual_gen.h"
 #include "rex_error.h"
 #include <algorithm>
@@ -1165,6 +1166,57 @@ int rex_dynamics(RexSim* s, const int32_t* d_env_ids, int n, const RexDynamicsOu
     return failf(REX_EINVAL, "%s: mass_matrix and toe_jacobian must be 16-byte aligned", who);
   HIPCHK(hipSetDevice(s->device));
   HIPCHK(rex_launch_dynamics(s, d_env_ids, n, *out, (hipStream_t)stream));
+  return REX_OK;
+}
+
+static_assert(sizeof(RexDynamicsLoad) == 24, "RexDynamicsLoad: 3 pointers, no padding (rex_gym_amd/_lib.py mirrors it)");
+
+// what the three solves with M refuse alike: the null and range cases of rex_dynamics, mark arm
+static int solve_rows(const char* who, RexSim* s, const int32_t* d_env_ids, int n) {
+  const int rows_err = sense_rows(who, s, d_env_ids, n);
+  if (rows_err != REX_OK) return rows_err;
+  if (s->cfg.mark == REX_MARK_ARM) return failf(REX_EINVAL, "%s: mark arm is not supported (18 degrees of freedom only)", who);
+  if ((long long)n * rex::kDynDof >= (1ll << 31)) return failf(REX_EINVAL, "%s: n %d: n * 18 must stay below 2^31", who, n);
+  return REX_OK;
+}
+
+int rex_dynamics_solve(RexSim* s, const int32_t* d_env_ids, int n, int K, const float* d_rhs, float* d_x, void* stream) {
+  const char* who = "rex_dynamics_solve";
+  if (!d_rhs || !d_x) return failf(REX_EINVAL, "%s: null pointer", who);
+  const int rows_err = solve_rows(who, s, d_env_ids, n);
+  if (rows_err != REX_OK) return rows_err;
+  if (K < 1) return failf(REX_EINVAL, "%s: K %d: at least one right-hand side per row", who, K);
+  if ((long long)n * K * rex::kDynDof >= (1ll << 31)) return failf(REX_EINVAL, "%s: n %d, K %d: n * K * 18 must stay below 2^31", who, n, K);
+  const uintptr_t r0 = (uintptr_t)d_rhs, x0 = (uintptr_t)d_x, bytes = (uintptr_t)n * K * rex::kDynDof * sizeof(float);
+  if (r0 != x0 && r0 < x0 + bytes && x0 < r0 + bytes)
+    return failf(REX_EINVAL, "%s: d_rhs and d_x overlap in part (the same pointer solves in place; otherwise they must be disjoint)", who);
+  rex::RexSolveArgs a{rex::kSolveRhs, K, d_rhs, d_x, nullptr, nullptr, nullptr, nullptr};
+  HIPCHK(hipSetDevice(s->device));
+  HIPCHK(rex_launch_dynamics_solve(s, d_env_ids, n, a, (hipStream_t)stream));
+  return REX_OK;
+}
+
+int rex_forward_dynamics(RexSim* s, const int32_t* d_env_ids, int n, const RexDynamicsLoad* load, float* d_vdot, void* stream) {
+  const char* who = "rex_forward_dynamics";
+  if (!load || !d_vdot) return failf(REX_EINVAL, "%s: null pointer", who);
+  const int rows_err = solve_rows(who, s, d_env_ids, n);
+  if (rows_err != REX_OK) return rows_err;
+  rex::RexSolveArgs a{rex::kSolveForward, 1, nullptr, d_vdot, load->joint, load->toe, load->base, nullptr};
+  HIPCHK(hipSetDevice(s->device));
+  HIPCHK(rex_launch_dynamics_solve(s, d_env_ids, n, a, (hipStream_t)stream));
+  return REX_OK;
+}
+
+int rex_apply_impulse(RexSim* s, const int32_t* d_env_ids, int n, const RexDynamicsLoad* impulse, float* d_dv, void* stream) {
+  const char* who = "rex_apply_impulse";
+  if (!impulse) return failf(REX_EINVAL, "%s: null pointer", who);
+  const int rows_err = solve_rows(who, s, d_env_ids, n);
+  if (rows_err != REX_OK) return rows_err;
+  if (!impulse->joint && !impulse->toe && !impulse->base) return failf(REX_EINVAL, "%s: every impulse pointer is null", who);
+  if (s->cfg.on_rack) return failf(REX_EINVAL, "%s: an on_rack sim holds its base with an anchor the solve leaves out", who);
+  rex::RexSolveArgs a{rex::kSolveImpulse, 1, nullptr, d_dv, impulse->joint, impulse->toe, impulse->base, s->d_state};
+  HIPCHK(hipSetDevice(s->device));
+  HIPCHK(rex_launch_dynamics_solve(s, d_env_ids, n, a, (hipStream_t)stream));
   return REX_OK;
 }
 

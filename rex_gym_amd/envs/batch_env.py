@@ -648,6 +648,35 @@ class RexBatchEnv:
         from .. import dynamics
         return dynamics.read(self, env_ids, fields, out)
 
+    def dynamics_solve(self, rhs, env_ids=None, out=None):
+        """x = M(q)^-1 rhs at the current state (rex_dynamics_solve), one launch on the env's device and stream, no host sync; M is
+        never written out.  rhs: float32 [k, 18] or [k, K, 18] on the device, contiguous (rows and env_ids as in dynamics()); returns
+        a tensor of the same shape.  out: a tensor of that shape to fill; out=rhs solves in place.  The Delassus matrix of the toe
+        points is J M^-1 J^T:  J = env.dynamics(fields=("toe_jacobian",)).toe_jacobian.view(k, 24, 18);
+        W = torch.einsum("kpd,kqd->kpq", J, env.dynamics_solve(J)).  Mark 'arm' raises NotImplementedError.  Every argument error is
+        raised before any launch."""
+        from .. import dynamics
+        return dynamics.solve(self, rhs, env_ids, out)
+
+    def forward_dynamics(self, tau=None, toe_forces=None, base_wrench=None, env_ids=None, out=None):
+        """vdot [k, 18] = M^-1 (S^T tau + sum_p J_p^T f_p + w - bias) at the current state (rex_forward_dynamics): the acceleration
+        the rigid-body equation of dynamics() gives for joint torques tau [k, 12], world forces toe_forces [k, 4, 2, 3] at the toe
+        points (kinematics().toe_pos) and base_wrench [k, 6] -- a world force at the base origin, then a world moment.  float32
+        device tensors; one without the row dimension ([12], [4, 2, 3], [6]) holds for every row; None is zero, and at least one
+        must be given.  Like bias it leaves out the sim's damping, joint limits, contacts and the on_rack anchor.  Read-only."""
+        from .. import dynamics
+        return dynamics.forward(self, tau, toe_forces, base_wrench, env_ids, out)
+
+    def push(self, base_impulse=None, toe_impulses=None, joint_impulses=None, env_ids=None, out=None):
+        """An external push between two control steps (rex_apply_impulse): the impulses -- base_impulse [k, 6] (N s at the base
+        origin, then N m s), toe_impulses [k, 4, 2, 3] at the toe points, joint_impulses [k, 12]; shapes and None as the loads of
+        forward_dynamics() -- change the generalized velocity by dv = M^-1 (generalized impulse).  dv [k, 18] is ADDED to the
+        base's linear and angular velocity and the joint rates of the envs in the state, and returned.  Nothing else in the state
+        changes; the next step() starts from the pushed velocities.  Raises before any launch: before the first reset()
+        (RuntimeError), duplicate env_ids (ValueError), mark 'arm' (NotImplementedError), an on_rack env (ValueError)."""
+        from .. import dynamics
+        return dynamics.push(self, base_impulse, toe_impulses, joint_impulses, env_ids, out)
+
     def _action_bounds(self):
         if self._act_lo is None:
             torch = self._torch
