@@ -635,6 +635,50 @@ REX_API int rex_forward_dynamics(RexSim* sim, const int32_t* d_env_ids, int n, c
 REX_API int rex_apply_impulse(RexSim* sim, const int32_t* d_env_ids, int n, const RexDynamicsLoad* impulse, float* d_dv /* nullable */,
                               void* stream);
 
+/* The contact solve (csrc/rex_contact_solve.h): ground reaction forces at the toe points, joint-limit torques and the
+ * contact-consistent next velocity of every row's env -- ONE substep of the step's physics restated for the current state and solved
+ * in a read-only launch of its own.  The step, settle and reset kernels are not involved and the state is never written.  Mark base
+ * only.  Rows, ids and launch as rex_dynamics: no host sync; v, the order of its 18 components, M, h, J_p, the masses (with the
+ * env's scales) and the toe points p = 2 leg + e are rex_dynamics'; mu is the env's toe friction.
+ *   1. Free velocity  v* = v + dt M^-1 (S^T tau - h(q, v) - d(q, v)),  d the generalized force of the sim's per-link damping: on every
+ *      body a force m (0.04 + 0.04 |vc|) vc at the centre of mass and a moment I w (0.04 + 0.04 |w|).  damping = 0 leaves d out: the
+ *      result then sits on the equation of rex_forward_dynamics.
+ *   2. Rows, in the solver's order.  (a) Joint-limit rows j = 0..11, only for a joint beyond its bound, gap = min(q - lower,
+ *      upper - q) < 0:  J = sgn e_j, 0 <= lambda, rhs = (-gap 0.2 / dt - sgn v*_j) / diag.  (b) Normal rows of the toe points in reach
+ *      (dist < 0.02 m), in order of p:  J = n^T J_p, 0 <= lambda, rhs = (poserr + velerr) / diag with velerr = -J v* - (dist > 0 ?
+ *      dist / dt : 0) and poserr = dist > 0 ? 0 : -dist 0.2 / dt.  (c) Friction rows in order of p, two per point:  J = t1^T J_p,
+ *      t2^T J_p with (t1, t2) Bullet's btPlaneSpace1 of n, rhs = -(J v*) / diag, |lambda| <= mu lambda_n of the normal row's current
+ *      value.  diag = J M^-1 J^T.
+ *   3. Projected Gauss-Seidel from lambda = 0: each sweep visits the rows in that order, dl = rhs - (J dv) / diag clamped so that
+ *      lambda stays in its bounds, dv += M^-1 J^T dl; it stops after `iterations` sweeps or after the first sweep whose largest
+ *      (dl diag)^2 is <= residual_threshold.
+ *   4. v_next = clamp(v* + dv, +-100).
+ * What it takes for the result to be the step's own forces: the step draws tau from the motor model anew in every substep
+ * (rex_motor_torque_params reproduces it); the state holds no last torque, so the caller supplies tau.  Link-box rows
+ * (body_contacts) and the on_rack anchor are not restated: such sims are refused.
+ * Outputs (any member may be NULL; each needs the alignment of its element):  toe_force, the world force on the foot at the toe
+ * point (rex_kinematics' toe_pos), N = impulse / dt, 0 for a point out of reach;  toe_lambda, the (normal, t1, t2) impulses, N s;
+ * limit_torque, the signed joint torque of the limit rows, N m;  v_next;  sweeps, the env's own sweep count.
+ * v_next = v + dt vdot with vdot = rex_forward_dynamics(tau + limit_torque, toe_force) when damping = 0 and no component is clamped.
+ * REX_EINVAL (message in rex_last_error) without a launch for: a null sim, in or out; n < 1; n > num_envs without ids; n * 24 >=
+ * 2^31; an `out` whose members are all NULL; iterations > 1000; a non-finite dt or threshold; a sim of mark arm, on_rack or with
+ * body_contacts. */
+typedef struct RexContactSolveIn {
+  const float* tau;            /* [n][12] joint torques, or NULL: zero */
+  float dt;                    /* <= 0: cfg.sim_time_step */
+  int32_t iterations;          /* <= 0: cfg.solver_iterations */
+  float residual_threshold;    /* < 0: cfg.solver_residual_threshold; 0: always `iterations` sweeps */
+  int32_t damping;             /* 1: with the sim's damping forces (what the step does); 0: without */
+} RexContactSolveIn;
+typedef struct RexContactSolveOut {     /* any member may be NULL */
+  float* toe_force;            /* [n][4][2][3] world force on the foot at kinematics' toe_pos, N = impulse / dt; 0 out of reach */
+  float* toe_lambda;           /* [n][4][2][3] (normal, t1, t2) impulses, N s */
+  float* limit_torque;         /* [n][12] signed joint torque of the limit rows, N m */
+  float* v_next;               /* [n][18] */
+  int32_t* sweeps;             /* [n] */
+} RexContactSolveOut;
+REX_API int rex_contact_solve(RexSim* sim, const int32_t* d_env_ids, int n, const RexContactSolveIn* in, const RexContactSolveOut* out, void* stream);
+
 /* ---- the fused PPO learner (csrc/rex_learner.h): the losses of the reference's KL-penalty PPO (agents/ppo/algorithm.py:289-301,
  * 376-434) and their parameter gradients for a ForwardGaussianPolicy network (networks.py:69-112: obs_dim -> hidden1 -> hidden2 ->
  * out_dim, two ReLU layers), one pass over the episode memory per call.  Stateless: no RexSim, the library allocates nothing -- the

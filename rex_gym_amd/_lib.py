@@ -97,6 +97,19 @@ class RexDynamicsLoad(ctypes.Structure):
     _fields_ = [("joint", ctypes.c_void_p), ("toe", ctypes.c_void_p), ("base", ctypes.c_void_p)]
 
 
+class RexContactSolveIn(ctypes.Structure):
+    """Mirror of `struct RexContactSolveIn` (include/rexsim.h): the torques and the solver settings of rex_contact_solve (a value <= 0,
+    for the threshold < 0, takes the config's)."""
+    _fields_ = [("tau", ctypes.c_void_p), ("dt", ctypes.c_float), ("iterations", ctypes.c_int32), ("residual_threshold", ctypes.c_float),
+                ("damping", ctypes.c_int32)]
+
+
+class RexContactSolveOut(ctypes.Structure):
+    """Mirror of `struct RexContactSolveOut` (include/rexsim.h): the device arrays rex_contact_solve fills (a null one is skipped)."""
+    _fields_ = [("toe_force", ctypes.c_void_p), ("toe_lambda", ctypes.c_void_p), ("limit_torque", ctypes.c_void_p), ("v_next", ctypes.c_void_p),
+                ("sweeps", ctypes.c_void_p)]
+
+
 class RexPpoNet(ctypes.Structure):
     """Mirror of `struct RexPpoNet` (include/rexsim.h): a two-layer ReLU network of the fused learner, torch layout."""
     _fields_ = [("obs_dim", ctypes.c_int32), ("out_dim", ctypes.c_int32), ("hidden1", ctypes.c_int32), ("hidden2", ctypes.c_int32),
@@ -198,6 +211,8 @@ _SIGS = {
     "rex_dynamics_solve": ([ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p], ctypes.c_int),
     "rex_forward_dynamics": ([ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(RexDynamicsLoad), ctypes.c_void_p, ctypes.c_void_p], ctypes.c_int),
     "rex_apply_impulse": ([ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(RexDynamicsLoad), ctypes.c_void_p, ctypes.c_void_p], ctypes.c_int),
+    "rex_contact_solve": ([ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(RexContactSolveIn), ctypes.POINTER(RexContactSolveOut),
+                           ctypes.c_void_p], ctypes.c_int),
     "rex_ppo_workspace_bytes": ([ctypes.c_int] * 6, ctypes.c_longlong),
     "rex_ppo_returns": ([ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_float, ctypes.c_void_p, ctypes.c_void_p,
                          ctypes.c_float, ctypes.c_void_p, ctypes.c_void_p], ctypes.c_int),

@@ -1,4 +1,4 @@
-// rex_dynamics_leg.h -- the front end that the kernels of the equations of motion share (rex_dynamics.hip, rex_dynamics_solve.hip):
+// rex_dynamics_leg.h -- the front end that the kernels of the equations of motion share (rex_dynamics.hip, rex_dynamics_solve.hip, rex_contact_solve.hip):
 // one lane per (output row, leg) walks its leg's chain in LDS with the renderer's functions, holds the leg in registers (DynLeg),
 // forms the composite rigid bodies about the base origin o_0 and from them the leg's columns of the mass matrix -- the coupling
 // B_f (6 x 3, column i = (f_i, n_i)) and the leg block H_f (3 x 3) -- and, by DPP quad sums, the base block; leg_bias is the

@@ -135,3 +135,5 @@ hipError_t rex_launch_render(const RexSim* s, const rex::RenderCam& cam, const i
 #include "rex_dynamics.hip"
 // solves with that mass matrix (rex_dynamics_solve, rex_forward_dynamics, rex_apply_impulse): the same front end, M kept in registers
 #include "rex_dynamics_solve.hip"
+// one substep's contact problem at that state (rex_contact_solve): the same front end and factors, then the step's projected Gauss-Seidel
+#include "rex_contact_solve.hip"

@@ -12,6 +12,7 @@
 #include "rex_kinematics.h"
 #include "rex_dynamics.h"
 #include "rex_dynamics_solve.h"
+#include "rex_contact_solve.h"
 #include "rex_visual_gen.h"
 #include "rex_error.h"
 #include <algorithm>
@@ -1217,6 +1218,29 @@ int rex_apply_impulse(RexSim* s, const int32_t* d_env_ids, int n, const RexDynam
   rex::RexSolveArgs a{rex::kSolveImpulse, 1, nullptr, d_dv, impulse->joint, impulse->toe, impulse->base, s->d_state};
   HIPCHK(hipSetDevice(s->device));
   HIPCHK(rex_launch_dynamics_solve(s, d_env_ids, n, a, (hipStream_t)stream));
+  return REX_OK;
+}
+
+static_assert(sizeof(RexContactSolveIn) == 24 && sizeof(RexContactSolveOut) == 40, "RexContactSolveIn: a pointer, four 4-byte words; RexContactSolveOut: 5 pointers (rex_gym_amd/_lib.py mirrors them)");
+
+int rex_contact_solve(RexSim* s, const int32_t* d_env_ids, int n, const RexContactSolveIn* in, const RexContactSolveOut* out, void* stream) {
+  const char* who = "rex_contact_solve";
+  if (!in || !out) return failf(REX_EINVAL, "%s: null pointer", who);
+  const int rows_err = solve_rows(who, s, d_env_ids, n);
+  if (rows_err != REX_OK) return rows_err;
+  if ((long long)n * 24 >= (1ll << 31)) return failf(REX_EINVAL, "%s: n %d: n * 24 must stay below 2^31", who, n);
+  if (s->cfg.on_rack) return failf(REX_EINVAL, "%s: an on_rack sim holds its base with an anchor the solve leaves out", who);
+  if (s->cfg.body_contacts) return failf(REX_EINVAL, "%s: a sim with body_contacts solves link-box rows the solve leaves out", who);
+  if (!out->toe_force && !out->toe_lambda && !out->limit_torque && !out->v_next && !out->sweeps)
+    return failf(REX_EINVAL, "%s: every output pointer is null", who);
+  rex::RexContactArgs a{in->tau, in->dt > 0.0f ? in->dt : s->cfg.sim_time_step, in->iterations > 0 ? in->iterations : s->cfg.solver_iterations,
+                        in->residual_threshold < 0.0f ? s->cfg.solver_residual_threshold : in->residual_threshold, in->damping != 0, *out};
+  if (a.iterations < 1 || a.iterations > rex::kContactMaxIterations)
+    return failf(REX_EINVAL, "%s: iterations %d: 1 .. %d", who, a.iterations, rex::kContactMaxIterations);
+  if (!(a.dt > 0.0f) || !std::isfinite(a.dt) || !(a.threshold >= 0.0f) || !std::isfinite(a.threshold))
+    return failf(REX_EINVAL, "%s: dt %g, residual_threshold %g: a finite dt > 0 and a finite threshold", who, (double)in->dt, (double)in->residual_threshold);
+  HIPCHK(hipSetDevice(s->device));
+  HIPCHK(rex_launch_contact_solve(s, d_env_ids, n, a, (hipStream_t)stream));
   return REX_OK;
 }
 
