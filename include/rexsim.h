@@ -679,6 +679,44 @@ typedef struct RexContactSolveOut {     /* any member may be NULL */
 } RexContactSolveOut;
 REX_API int rex_contact_solve(RexSim* sim, const int32_t* d_env_ids, int n, const RexContactSolveIn* in, const RexContactSolveOut* out, void* stream);
 
+/* The acceleration level (csrc/rex_contact_space.h): what a whole-body controller, a force-distribution QP or an analytic contact model
+ * needs beside M, h and J_p -- each in one read-only launch, M(q) never written out, the state never written.  Mark base only.  Rows, ids
+ * and launch as rex_dynamics: no host sync; v, the order of its 18 components, M, h, J_p, the masses (with the env's scales) and the toe
+ * points p = 2 leg + e are rex_dynamics'.  Like `bias`, both calls leave out what the step adds to the rigid-body equation: the
+ * Bullet-style damping, joint-limit rows, contact rows and the on_rack anchor.
+ *
+ *   rex_inverse_dynamics  force [n][18] = M(q) vdot + h(q, v) - S^T tau - sum_p J_p^T f_p - w:  the equation of rex_forward_dynamics solved
+ *                         for the force.  vdot [n][18] is the wanted generalized acceleration (NULL: zero); the load is what is applied
+ *                         already -- joint torques `joint`, world forces `toe` at the toe points, the base wrench `base` -- and may be NULL,
+ *                         as may any member (zero).  force[6:18] is the joint torque still needed; force[0:6] is the force at the base
+ *                         origin and the moment that nothing supplies: zero for a motion the given ground forces can produce.  The ground
+ *                         is queried only when toe forces are given.  With everything NULL, force = h.
+ *   rex_contact_space     for joint torques d_tau [n][12] and a base wrench d_base_wrench [n][6] (either may be NULL: zero), any of
+ *     delassus     [n][24][24]  J M^-1 J^T of the eight toe points: row and column 3 p + c, world axis c, for all eight points whether in
+ *                               reach or not (as toe_jacobian).  Symmetric positive semidefinite; both triangles are written from one
+ *                               value per pair (they carry the same bits)
+ *     toe_drift    [n][8][3]    Jdot v: the acceleration of the foot link's material point at toe_pos[p] when vdot = 0.  With w_0 the
+ *                               base's angular velocity, w_i = w_i-1 + qd_i a_i and joint points o_i carried by their parents:
+ *                               alpha_0 = 0, acc(o_0) = 0;  alpha_i = alpha_i-1 + w_i-1 x (qd_i a_i);
+ *                               acc(o_i) = acc(o_i-1) + alpha_i-1 x (o_i - o_i-1) + w_i-1 x (w_i-1 x (o_i - o_i-1));
+ *                               drift_p = acc(o_3) + alpha_3 x (P - o_3) + w_3 x (w_3 x (P - o_3))
+ *     toe_acc_free [n][8][3]    J_p M^-1 (S^T tau + w - h) + drift_p: the toe acceleration with no ground force.  With forces f [24] at
+ *                               the toe points the acceleration is toe_acc_free + delassus f
+ *   A NULL member of RexContactSpaceOut is not computed.  delassus is written in 16-byte chunks and must be 16-byte aligned (a row is
+ *   2 304 bytes); the other arrays need the alignment of a float.
+ * REX_EINVAL (message in rex_last_error) without a launch for: a null sim, force or out; n < 1; n > num_envs without ids; n * 18 >= 2^31;
+ * a sim of mark arm; and for rex_contact_space an `out` whose members are all NULL, n * 24 * 24 >= 2^31, a delassus that is not 16-byte
+ * aligned. */
+typedef struct RexContactSpaceOut {     /* any member may be NULL */
+  float* delassus;             /* [n][24][24] */
+  float* toe_drift;            /* [n][4][2][3] */
+  float* toe_acc_free;         /* [n][4][2][3] */
+} RexContactSpaceOut;
+REX_API int rex_inverse_dynamics(RexSim* sim, const int32_t* d_env_ids, int n, const float* d_vdot /* nullable */,
+                                 const RexDynamicsLoad* load /* nullable */, float* d_force, void* stream);
+REX_API int rex_contact_space(RexSim* sim, const int32_t* d_env_ids, int n, const float* d_tau /* nullable */,
+                              const float* d_base_wrench /* nullable */, const RexContactSpaceOut* out, void* stream);
+
 /* ---- the fused PPO learner (csrc/rex_learner.h): the losses of the reference's KL-penalty PPO (agents/ppo/algorithm.py:289-301,
  * 376-434) and their parameter gradients for a ForwardGaussianPolicy network (networks.py:69-112: obs_dim -> hidden1 -> hidden2 ->
  * out_dim, two ReLU layers), one pass over the episode memory per call.  Stateless: no RexSim, the library allocates nothing -- the

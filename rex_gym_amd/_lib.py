@@ -110,6 +110,11 @@ class RexContactSolveOut(ctypes.Structure):
                 ("sweeps", ctypes.c_void_p)]
 
 
+class RexContactSpaceOut(ctypes.Structure):
+    """Mirror of `struct RexContactSpaceOut` (include/rexsim.h): the device arrays rex_contact_space fills (a null one is skipped)."""
+    _fields_ = [("delassus", ctypes.c_void_p), ("toe_drift", ctypes.c_void_p), ("toe_acc_free", ctypes.c_void_p)]
+
+
 class RexPpoNet(ctypes.Structure):
     """Mirror of `struct RexPpoNet` (include/rexsim.h): a two-layer ReLU network of the fused learner, torch layout."""
     _fields_ = [("obs_dim", ctypes.c_int32), ("out_dim", ctypes.c_int32), ("hidden1", ctypes.c_int32), ("hidden2", ctypes.c_int32),
@@ -212,6 +217,10 @@ _SIGS = {
     "rex_forward_dynamics": ([ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(RexDynamicsLoad), ctypes.c_void_p, ctypes.c_void_p], ctypes.c_int),
     "rex_apply_impulse": ([ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(RexDynamicsLoad), ctypes.c_void_p, ctypes.c_void_p], ctypes.c_int),
     "rex_contact_solve": ([ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(RexContactSolveIn), ctypes.POINTER(RexContactSolveOut),
+                           ctypes.c_void_p], ctypes.c_int),
+    "rex_inverse_dynamics": ([ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(RexDynamicsLoad), ctypes.c_void_p,
+                              ctypes.c_void_p], ctypes.c_int),
+    "rex_contact_space": ([ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(RexContactSpaceOut),
                            ctypes.c_void_p], ctypes.c_int),
     "rex_ppo_workspace_bytes": ([ctypes.c_int] * 6, ctypes.c_longlong),
     "rex_ppo_returns": ([ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_float, ctypes.c_void_p, ctypes.c_void_p,

@@ -137,3 +137,5 @@ hipError_t rex_launch_render(const RexSim* s, const rex::RenderCam& cam, const i
 #include "rex_dynamics_solve.hip"
 // one substep's contact problem at that state (rex_contact_solve): the same front end and factors, then the step's projected Gauss-Seidel
 #include "rex_contact_solve.hip"
+// the acceleration level (rex_contact_space, rex_inverse_dynamics): the same front end and factors, the toe points' Delassus matrix
+#include "rex_contact_space.hip"

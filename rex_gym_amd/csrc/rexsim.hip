@@ -13,6 +13,7 @@
 #include "rex_dynamics.h"
 #include "rex_dynamics_solve.h"
 #include "rex_contact_solve.h"
+#include "rex_contact_space.h"
 #include "rex_visual_gen.h"
 #include "rex_error.h"
 #include <algorithm>
@@ -1241,6 +1242,35 @@ int rex_contact_solve(RexSim* s, const int32_t* d_env_ids, int n, const RexConta
     return failf(REX_EINVAL, "%s: dt %g, residual_threshold %g: a finite dt > 0 and a finite threshold", who, (double)in->dt, (double)in->residual_threshold);
   HIPCHK(hipSetDevice(s->device));
   HIPCHK(rex_launch_contact_solve(s, d_env_ids, n, a, (hipStream_t)stream));
+  return REX_OK;
+}
+
+static_assert(sizeof(RexContactSpaceOut) == 24, "RexContactSpaceOut: 3 pointers, no padding (rex_gym_amd/_lib.py mirrors it)");
+
+int rex_inverse_dynamics(RexSim* s, const int32_t* d_env_ids, int n, const float* d_vdot, const RexDynamicsLoad* load, float* d_force, void* stream) {
+  const char* who = "rex_inverse_dynamics";
+  if (!d_force) return failf(REX_EINVAL, "%s: null pointer", who);
+  const int rows_err = solve_rows(who, s, d_env_ids, n);
+  if (rows_err != REX_OK) return rows_err;
+  rex::RexInverseArgs a{d_vdot, load ? load->joint : nullptr, load ? load->toe : nullptr, load ? load->base : nullptr, d_force};
+  HIPCHK(hipSetDevice(s->device));
+  HIPCHK(rex_launch_inverse_dynamics(s, d_env_ids, n, a, (hipStream_t)stream));
+  return REX_OK;
+}
+
+int rex_contact_space(RexSim* s, const int32_t* d_env_ids, int n, const float* d_tau, const float* d_base_wrench, const RexContactSpaceOut* out,
+                      void* stream) {
+  const char* who = "rex_contact_space";
+  if (!out) return failf(REX_EINVAL, "%s: null pointer", who);
+  const int rows_err = solve_rows(who, s, d_env_ids, n);
+  if (rows_err != REX_OK) return rows_err;
+  if ((long long)n * rex::kDelassusFloats >= (1ll << 31)) return failf(REX_EINVAL, "%s: n %d: n * 24 * 24 must stay below 2^31", who, n);
+  if (!out->delassus && !out->toe_drift && !out->toe_acc_free) return failf(REX_EINVAL, "%s: every output pointer is null", who);
+  if ((uintptr_t)out->delassus & 15u)                        // (the kernel writes it in 16-byte chunks)
+    return failf(REX_EINVAL, "%s: delassus must be 16-byte aligned", who);
+  rex::RexContactSpaceArgs a{d_tau, d_base_wrench, *out};
+  HIPCHK(hipSetDevice(s->device));
+  HIPCHK(rex_launch_contact_space(s, d_env_ids, n, a, (hipStream_t)stream));
   return REX_OK;
 }
 

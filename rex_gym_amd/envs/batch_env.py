@@ -697,6 +697,31 @@ class RexBatchEnv:
         from .. import contact
         return contact.solve(self, tau, env_ids, fields, out, dt, iterations, residual_threshold, damping)
 
+    # ---- the acceleration level (rex_gym_amd/contact_space.py) ----
+    def inverse_dynamics(self, vdot=None, tau=None, toe_forces=None, base_wrench=None, env_ids=None, out=None):
+        """need [k, 18] = M vdot + bias - S^T tau - sum_p J_p^T f_p - w at the current state (rex_inverse_dynamics): the equation of
+        forward_dynamics() solved for the force, one read-only launch, M never written out.  vdot [k, 18] is the wanted generalized
+        acceleration; tau [k, 12], toe_forces [k, 4, 2, 3] and base_wrench [k, 6] are what is applied already (shapes, broadcasting
+        and None = zero as in forward_dynamics(); all None is allowed: need = bias).  need[:, 6:] is the joint torque still
+        needed; need[:, :6] is the force at the base origin and the moment that nothing supplies -- zero for a motion the given
+        ground forces can produce.  Mark 'arm' raises NotImplementedError.  Every argument error is raised before any launch."""
+        from .. import contact_space
+        return contact_space.inverse(self, vdot, tau, toe_forces, base_wrench, env_ids, out)
+
+    def contact_space(self, tau=None, base_wrench=None, fields=None, env_ids=None, out=None):
+        """The contact-space quantities of the 8 toe points at the current state (rex_contact_space), one read-only launch on the
+        env's device and stream, no host sync.  Returns a contact_space.ContactSpace whose attributes are float32 tensors of k rows
+        (env_ids as in render()), conventions of dynamics():
+          delassus [k, 24, 24]: J M^-1 J^T, row and column 3 p + c for point p = 2 leg + end and world axis c, for all eight
+              points whether in reach or not; symmetric, both triangles the same bits
+          toe_drift [k, 4, 2, 3]: Jdot v, the acceleration of the foot's material point at kinematics().toe_pos when vdot = 0
+          toe_acc_free [k, 4, 2, 3]: J M^-1 (S^T tau + w - bias) + toe_drift for joint torques tau [k, 12] or [12] and
+              base_wrench [k, 6] or [6] (None: zero): the toe acceleration with no ground force
+        With ground forces f the toe acceleration is toe_acc_free + delassus f.  fields, out: as in kinematics().  Mark 'arm'
+        raises NotImplementedError.  Every argument error is raised before any launch."""
+        from .. import contact_space
+        return contact_space.read(self, tau, base_wrench, fields, env_ids, out)
+
     def _action_bounds(self):
         if self._act_lo is None:
             torch = self._torch
