@@ -9,7 +9,9 @@
     then the lowest point of the end's rim along it, then the height and normal under that point -- with rexsim's rule beside the
     footprint (the grid coordinate is clamped to [0, n - 1 - 0.001]: the border's height holds on) and the facet ids of both queries.
 
-A field is field_cast's tuple (heights [ny * nx], mid, nx, ny, 1 / cell_x, 1 / cell_y, off_x, off_y); None is the plane."""
+A field is field_cast's tuple (heights [ny * nx], mid, nx, ny, 1 / cell_x, 1 / cell_y, off_x, off_y); None is the plane.  The grid
+constants -- 1 / cell, the offsets, the clamp limit -- are float32 values formed in float32 arithmetic, as the product's host code and the
+oracle hold them (grid_constants, clamp_limit); the random pool's 20, 127.5 are exact and its limit is 254.999f."""
 import math
 import re
 
@@ -68,6 +70,22 @@ def quat_of(R):
     return q if q[3] >= 0 else -q
 
 
+def clamp_limit(n):
+    """the largest grid coordinate of an axis of n vertices as the product holds it: a float32 value, formed in float32 arithmetic
+    (csrc/rexsim.hip rex_set_heightfield: `g.max_x = (float)(nx - 1) - 0.001f`; for n = 256 that is the 254.999f of rex_set_terrain and
+    of HF_RANDOM in oracle/rex_oracle.c), widened"""
+    return float(np.float32(n - 1) - np.float32(0.001))
+
+
+def grid_constants(n, cell, origin):
+    """-> (1 / cell, offset) of one axis as csrc/rexsim.hip rex_set_heightfield and orc_set_heightfield of oracle/rex_oracle.c form them
+    (`g.inv_cx = 1.0f / cell_x; g.off_x = 0.5f * (float)(nx - 1) - origin_x * g.inv_cx`): float32 arithmetic, then widened, so that the
+    reference stands on the grid the kernels see and not on one 1e-8 m beside it"""
+    f = np.float32
+    inv = f(1) / f(cell)
+    return float(inv), float(f(0.5) * f(n - 1) - f(origin) * inv)
+
+
 def ground_query(field, x, y, dtype=np.float64):
     """-> (height over the z = 0 plane, unit normal [3], facet id): the facet the point (x, y) stands on, 1 + 2 (cell index) + (upper
     triangle), where it is above the plane; else the plane, id 0"""
@@ -76,8 +94,8 @@ def ground_query(field, x, y, dtype=np.float64):
     if field is None:
         return f(0), up, 0
     h, mid, nx, ny, inv_x, inv_y, off_x, off_y = field
-    fx = min(max(f(x) * f(inv_x) + f(off_x), f(0)), f(nx - 1) - f(0.001))
-    fy = min(max(f(y) * f(inv_y) + f(off_y), f(0)), f(ny - 1) - f(0.001))
+    fx = min(max(f(x) * f(inv_x) + f(off_x), f(0)), f(clamp_limit(nx)))
+    fy = min(max(f(y) * f(inv_y) + f(off_y), f(0)), f(clamp_limit(ny)))
     i, j = int(fx), int(fy)
     u, v = fx - f(i), fy - f(j)
     h00, h10, h01, h11 = (f(h[j * nx + i]), f(h[j * nx + i + 1]), f(h[(j + 1) * nx + i]), f(h[(j + 1) * nx + i + 1]))
@@ -206,9 +224,8 @@ def scene_fields(ground, heights=None, mids=None):
         return [random_terrain_field(heights, mids, t) for t in range(POOL)]
     fields = custom_fields() if heights is None else heights
     mids = custom_mids(fields) if mids is None else mids
-    inv_x, inv_y = 1.0 / CUSTOM_CELL[0], 1.0 / CUSTOM_CELL[1]
-    return [(np.asarray(fields[t], np.float64).reshape(-1), float(mids[t]), CUSTOM_NX, CUSTOM_NY, inv_x, inv_y,
-             0.5 * (CUSTOM_NX - 1) - CUSTOM_ORIGIN[0] * inv_x, 0.5 * (CUSTOM_NY - 1) - CUSTOM_ORIGIN[1] * inv_y) for t in range(2)]
+    (inv_x, off_x), (inv_y, off_y) = grid_constants(CUSTOM_NX, CUSTOM_CELL[0], CUSTOM_ORIGIN[0]), grid_constants(CUSTOM_NY, CUSTOM_CELL[1], CUSTOM_ORIGIN[1])
+    return [(np.asarray(fields[t], np.float64).reshape(-1), float(mids[t]), CUSTOM_NX, CUSTOM_NY, inv_x, inv_y, off_x, off_y) for t in range(2)]
 
 
 def field_of(fields, g, episode, env_index_base=0):

@@ -86,11 +86,12 @@ def assert_cases_cover(seen):
 
 
 # ---------------------------------------------------------------- the GPU's side
-def make_env(mark, n, ground):
-    """The env of a scene: reset, 8 random steps, then the synthetic columns written over all but the first few envs."""
+def make_env(mark, n, ground, **extra):
+    """The env of a scene: reset, 8 random steps, then the synthetic columns written over all but the first few envs.  `extra`: further
+    keywords of RexBatchEnv (tests/test_gpu_step_readout.py)."""
     import torch
     from rex_gym_amd import RexBatchEnv
-    kw = dict(task="walk", signal_type="ik", mark=mark, seed=5)
+    kw = dict(task="walk", signal_type="ik", mark=mark, seed=5, **extra)
     if ground == "random":
         kw.update(terrain_type="random", terrain_pool=kr.POOL)
     elif ground == "custom":
