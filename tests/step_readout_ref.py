@@ -88,22 +88,36 @@ def real_family(n, ground, count):
     return st[0:37, :count].astype(np.float32), st[orclib.S_EPISODE, :count].astype(np.int64), cmd[:count]
 
 
-def motor_tau(cmd, state, g, kp=1.0, kd=0.02):
+def motor_tau(cmd, state, g, kp=1.0, kd=0.02, q_obs=None, qd_obs=None, observed=False):
     """The torque the substep applies to env g (float64): the motor model on (cmd, q, qd, qd) -- with no latency the PD loop sees the
-    substep's own joint angles and rates (csrc/rex_kernels.h rex_substep) -- for enabled motors"""
+    substep's own joint angles and rates (csrc/rex_kernels.h rex_substep) -- for enabled motors.  q_obs, qd_obs [12]: what the PD loop
+    sees under the latency model (the true rate stays the state's); observed: the torque the sensor reports instead (motor.py:127-129)"""
     s = np.asarray(state[:, g], np.float64)
-    return _motor().motor_torque(cmd, s[13:25], s[25:37], s[25:37], kp, kd)[0]
+    q = s[13:25] if q_obs is None else np.asarray(q_obs, np.float64)
+    qd = s[25:37] if qd_obs is None else np.asarray(qd_obs, np.float64)
+    return _motor().motor_torque(cmd, q, qd, s[25:37], kp, kd)[1 if observed else 0]
 
 
-def motor_tau_params(cmd, state, g, voltage, damping, kp, kd, strength):
+def motor_tau_params(cmd, state, g, voltage, damping, kp, kd, strength, q_obs=None, qd_obs=None, observed=False):
     """motor_tau for an actuator with its own parameters (float64; strength [12]): the motor model of the reference's model/motor.py as
     include/rexsim.h states it for rex_motor_torque_params -- pwm = clip(kp (cmd - q) - kd qd, +-1), net voltage clip(pwm V - (Kt + damping)
-    qd, +-50), current = that / R, torque = strength x sign x interp(|current|, the table) -- R 0.186 ohm, Kt 0.0954"""
+    qd, +-50), current = that / R, torque = strength x sign x interp(|current|, the table) -- R 0.186 ohm, Kt 0.0954; the observed
+    torque clip(Kt pwm V / R, +-5.7) carries no strength ratio (motor.py:127-129)"""
     s = np.asarray(state[:, g], np.float64)
-    q, qd = s[13:25], s[25:37]
-    pwm = np.clip(-1.0 * kp * (q - np.asarray(cmd, np.float64)) - kd * qd, -1.0, 1.0)
-    cur = np.clip(pwm * voltage - (0.0954 + damping) * qd, -50.0, 50.0) / 0.186
-    return np.asarray(strength, np.float64) * np.sign(cur) * np.interp(np.abs(cur), [0, 10, 20, 30, 40, 50, 60], [0, 1, 1.9, 2.45, 3.0, 3.25, 3.5])
+    q = s[13:25] if q_obs is None else q_obs
+    qd = s[25:37] if qd_obs is None else qd_obs
+    return motor_model(cmd, q, qd, s[25:37], voltage, damping, kp, kd, strength)[1 if observed else 0]
+
+
+def motor_model(cmd, q, qd, qd_true, voltage=32.0, damping=0.0, kp=1.0, kd=0.02, strength=1.0):
+    """-> (actual, observed) torque, float64, elementwise over arrays of any one shape: motor_tau_params' model on the angles and rates
+    the PD loop sees (q, qd) and the true rates (qd_true)"""
+    cmd, q, qd, qd_true = (np.asarray(x, np.float64) for x in (cmd, q, qd, qd_true))
+    pwm = np.clip(-1.0 * kp * (q - cmd) - kd * qd, -1.0, 1.0)
+    observed = np.clip(0.0954 * (pwm * voltage / 0.186), -5.7, 5.7)
+    cur = np.clip(pwm * voltage - (0.0954 + damping) * qd_true, -50.0, 50.0) / 0.186
+    actual = np.asarray(strength, np.float64) * np.sign(cur) * np.interp(np.abs(cur), [0, 10, 20, 30, 40, 50, 60], [0, 1, 1.9, 2.45, 3.0, 3.25, 3.5])
+    return actual, observed
 
 
 def motor_params(n, seed=91):

@@ -41,6 +41,14 @@ per wave unless said otherwise; profiles/step_readout.md has the CPU side):
     67 custom, 16 per wave    66/67    2.845e-04     4.290e-05
     67 custom, 64 per wave    66/67    3.594e-04     4.294e-05
     67 plane, actuators       67/67    8.42e-06      4.83e-05   1.40e-05, 1.40e-05, 2.00e-06, 9.01e-06   8.17e-04, 3.66e-05       0.48 0.48 0.13
+    67 plane, latency 1.3 ms           5.60e-06      5.01e-05   (4 per wave; 64: 6.31e-06, 4.99e-05)                              0.46 0.47 0.12
+    67 plane, latency 97.7 ms          6.92e-06      5.01e-05   (64 per wave: 4.78e-06, 4.99e-05)                                 0.46 0.49 0.11
+    67 custom, latency 1.3 ms          5.56e-05      4.36e-05                                                                     0.46 0.49 0.14
+    67 custom, latency 97.7 ms         5.56e-05      4.36e-05                                                                     0.47 0.48 0.12
+
+The latency rows (test_physics_under_the_delayed_torque): pd_latency / control_latency on, latency_ref.make_ring(S0) in env.history; tau
+is the motor model's on the PD-delayed joint angles and rates and the true rates of S0.  With the reference under the torque of the undelayed
+reading a. reads 2.4e-02 .. 2.0e-01 (median), with the delayed rate taken for the true one 1.5e-03 .. 3.6e-02.
 
 With the reference wrong on purpose a. reads 1.3e-01 (friction 0.5 for the env's own), 7.2e-02 (mass scales 1), 1.0e-01 (base and leg scale
 swapped), 2.3 (the pool's next field), 1.9e-02 (the torque off by 1 %)."""
@@ -49,6 +57,7 @@ import pytest
 
 import contact_solve_ref as cr
 import kinematics_ref as kr
+import latency_ref as lr
 import step_readout_ref as sr
 import test_gpu_contact_solve as tc
 import test_gpu_kinematics as tk
@@ -69,16 +78,18 @@ S_FLAGS, S_STEPS, S_EPISODE, S_MOTOR_EN, S_OVERHEAT = 43, 44, 45, 46, 47        
 F_DONE = 16
 
 
-def motor_tau_gpu(env, cmd, S0, params=None):
-    """rex_motor_torque (params None: the config's gains) or rex_motor_torque_params on (cmd, q0, qd0, qd0) -> tau [n, 12] on the device"""
+def motor_tau_gpu(env, cmd, S0, params=None, seen=None):
+    """rex_motor_torque (params None: the config's gains) or rex_motor_torque_params on (cmd, q0, qd0, qd0) -> tau [n, 12] on the device;
+    seen: (q, qd) [n, 12] device tensors, what the PD loop sees under the latency model, in place of the first q0, qd0"""
     import torch
     from rex_gym_amd import _lib
     n = env.num_envs
-    q, qd = S0[13:25].t().contiguous(), S0[25:37].t().contiguous()
+    qd = S0[25:37].t().contiguous()
+    q, qd_seen = (S0[13:25].t().contiguous(), qd) if seen is None else (seen[0].contiguous(), seen[1].contiguous())
     cmd = cmd.contiguous()
     act, obs = torch.zeros_like(cmd), torch.zeros_like(cmd)
     if params is None:
-        _lib.check(env._L.rex_motor_torque(12 * n, cmd.data_ptr(), q.data_ptr(), qd.data_ptr(), qd.data_ptr(), float(env.config.motor_kp),
+        _lib.check(env._L.rex_motor_torque(12 * n, cmd.data_ptr(), q.data_ptr(), qd_seen.data_ptr(), qd.data_ptr(), float(env.config.motor_kp),
                                            float(env.config.motor_kd), act.data_ptr(), obs.data_ptr(), env._stream_ptr()), "rex_motor_torque")
     else:
         par = np.zeros((n, 12, 5), np.float32)                 # kp, kd, voltage, damping, strength per problem
@@ -86,19 +97,22 @@ def motor_tau_gpu(env, cmd, S0, params=None):
             par[:, :, k] = params[name][:, None]
         par[:, :, 4] = params["strength"].T
         par = tc.dev(env, par)
-        _lib.check(env._L.rex_motor_torque_params(12 * n, cmd.data_ptr(), q.data_ptr(), qd.data_ptr(), qd.data_ptr(), par.data_ptr(),
+        _lib.check(env._L.rex_motor_torque_params(12 * n, cmd.data_ptr(), q.data_ptr(), qd_seen.data_ptr(), qd.data_ptr(), par.data_ptr(),
                                                   act.data_ptr(), obs.data_ptr(), env._stream_ptr()), "rex_motor_torque_params")
     torch.cuda.synchronize()
     return act
 
 
 class Case:
-    """one case run end to end; `share`: a Case of the same scene whose S0 (and what the reference says about S0 alone) is reused"""
+    """one case run end to end; `share`: a Case of the same scene whose S0 (and what the reference says about S0 alone) is reused;
+    `latency`: (pd, control) [s] -- the latency model on, latency_ref.make_ring(S0) in env.history under latency_ref.cursors: the PD loop sees
+    the delayed joint angles and rates, the back-EMF the true rates (tests/test_gpu_latency.py has the ring's own checks)"""
 
-    def __init__(self, n, ground, thr, motor=False, share=None):
+    def __init__(self, n, ground, thr, motor=False, share=None, latency=None):
         import torch
         self.n, self.ground, self.thr = n, ground, thr
-        self.env = env = tk.make_env("base", n, ground, solver_residual_threshold=thr, check_actions=False, **sr.STEP_KW)
+        lat = {} if latency is None else dict(pd_latency=latency[0], control_latency=latency[1])
+        self.env = env = tk.make_env("base", n, ground, solver_residual_threshold=thr, check_actions=False, **lat, **sr.STEP_KW)
         assert env.config.action_repeat == 1 and env.config.solver_iterations == cr.ITERATIONS and env.config.auto_reset == 0
         assert env.config.max_episode_steps == 0 and env.config.sim_time_step == np.float32(cr.DT)
         self.epw = env._L.rex_envs_per_wave(env._h)
@@ -110,16 +124,27 @@ class Case:
             env.set_motor_params(**self.params)
         if share is not None:
             env.state.copy_(share.S0)
+        seen = None
+        if latency is not None:
+            heads, lengths = lr.cursors(n, int(latency[0] / lr.DT), int(latency[1] / lr.DT))
+            ring = lr.make_ring(env.state.cpu().numpy(), lr.RING_SEED, heads)
+            env.history.copy_(torch.as_tensor(ring.reshape(env.history.shape), device=env.device))
+            env.state.view(torch.int32)[lr.hist_word()] = torch.as_tensor(lr.cursor(heads, lengths), device=env.device)
+            R0 = env.history.clone()
+            seen = lr.delayed_batch(ring, heads, lengths, latency[0], lr.DT)[0:24]            # float64 [24, n]: q, qd as the PD loop sees them
         S0 = self.S0 = env.state.clone()
         _, _, done, info = env.step(tc.dev(env, sr.actions(n)))
         torch.cuda.synchronize()
         self.S1, self.cmd, self.done = env.state.clone(), info["action"].clone(), done.cpu().numpy().astype(bool)
         env.state.copy_(S0)
+        if latency is not None:
+            env.history.copy_(R0)
         torch.cuda.synchronize()
         assert torch.equal(tc.bits(env.state), tc.bits(S0))
         self.s0, self.s1 = S0.cpu().numpy(), self.S1.cpu().numpy()
         assert np.all(self.s0[S_MOTOR_EN].view(np.int32) == sr.ALL_MOTORS)
-        self.tau = motor_tau_gpu(env, self.cmd, S0, self.params)
+        self.seen = seen
+        self.tau = motor_tau_gpu(env, self.cmd, S0, self.params, None if seen is None else (tc.dev(env, seen[0:12].T), tc.dev(env, seen[12:24].T)))
         self.con = env.contact_solve(tau=self.tau)
         torch.cuda.synchronize()
         self.untouched = torch.equal(tc.bits(env.state), tc.bits(S0))
@@ -132,14 +157,18 @@ class Case:
         cmd = self.cmd.cpu().numpy()
         p = self.params
         self.rows, self.geometry, self.ok, self.tau_ref = [], [], np.zeros(n, bool), np.zeros((n, 12))
+        self.again = []                                        # per env: the reference on S0 under another torque
         for g in range(n):
             fld = kr.field_of(fields, g, ep[g])
             if motor:
                 tau = sr.motor_tau_params(cmd[g], self.s0, g, float(p["voltage"][g]), float(p["damping"][g]), float(p["kp"][g]), float(p["kd"][g]), p["strength"][:, g])
             else:
-                tau = sr.motor_tau(cmd[g], self.s0, g, float(env.config.motor_kp), float(env.config.motor_kd))
+                obs = {} if seen is None else dict(q_obs=seen[0:12, g], qd_obs=seen[12:24, g])
+                tau = sr.motor_tau(cmd[g], self.s0, g, float(env.config.motor_kp), float(env.config.motor_kd), **obs)
             dyn = share.rows[g]["dyn"] if share is not None else None
             ref = cr.reference(self.s0, g, fld, (bp[0, g], bp[1, g]), float(bp[2, g]), tau, residual_threshold=sr.threshold32(thr), dyn=dyn)
+            self.again.append(lambda tau, g=g, fld=fld: cr.reference(self.s0, g, fld, (bp[0, g], bp[1, g]), float(bp[2, g]), tau,
+                                                                    residual_threshold=sr.threshold32(thr), dyn=self.rows[g]["dyn"]))
             geometry = share.geometry[g] if share is not None else cr.compared(self.s0, g, fld, ref, tk.BOUNDS["toe_dist"], tk.BOUNDS["toe_pos"])
             self.rows.append(ref)
             self.tau_ref[g] = tau
@@ -163,11 +192,13 @@ class Case:
 def cases():
     made = {}
 
-    def get(n, ground, thr, motor=False, epw=None):
-        key = (n, ground, thr, motor, epw)
+    def get(n, ground, thr, motor=False, epw=None, latency=None):
+        key = (n, ground, thr, motor, epw) + (() if latency is None else (latency,))
         if key not in made:
             share = made.get((67, "custom", 0.0, False, None)) if (n, ground) == (67, "custom") else None
-            made[key] = Case(n, ground, thr, motor, share)
+            if latency is not None:
+                share = get(n, ground, 0.0)
+            made[key] = Case(n, ground, thr, motor, share, latency)
         return made[key]
     yield get
     for c in made.values():
@@ -238,3 +269,28 @@ def test_heterogeneous_actuators(cases):
     plain = sr.motor_tau(c.cmd.cpu().numpy()[10], c.s0, 10)
     assert np.abs(plain - c.tau_ref[10]).max() > 0.05                     # the parameters do enter
     check(c, (67, "plane", 0.0, "actuators"))
+
+
+@pytest.mark.parametrize("epw", [4, 64])
+@pytest.mark.parametrize("ground", ["plane", "custom"])
+@pytest.mark.parametrize("latency", [(0.0013, 0.0037), (0.0977, 0.0985)], ids=["1.3ms", "97.7ms"])
+def test_physics_under_the_delayed_torque(cases, monkeypatch, latency, ground, epw):
+    """The latency model on (check C of tests/test_gpu_latency.py): the torque the step draws is the motor model's on the PD-delayed joint
+    angles and rates and the TRUE rates of S0 -- a. .. d. unchanged, the overheat counters counting the actual torque.  Teeth: the float64
+    reference under the torque of the undelayed reading, and of the delayed rate taken for the true one, misses a."""
+    base = cases(67, ground, 0.0)
+    monkeypatch.setenv("REX_ENVS_PER_WAVE", str(epw))
+    c = cases(67, ground, 0.0, epw=epw, latency=latency)
+    assert c.epw == epw and np.array_equal(c.s0[0:lr.hist_word()].view(np.int32), base.s0[0:lr.hist_word()].view(np.int32))
+    assert c.env.config.pd_latency == np.float32(latency[0]) and c.env.history is not None
+    check(c, (67, ground, 0.0, "epw %d" % epw, "latency", latency))
+    cmd, kp, kd = c.cmd.cpu().numpy().astype(np.float64), float(c.env.config.motor_kp), float(c.env.config.motor_kd)
+    q0, qd0 = c.s0[13:25].astype(np.float64), c.s0[25:37].astype(np.float64)
+    wrong = {"undelayed": sr.motor_model(cmd.T, q0, qd0, qd0, kp=kp, kd=kd)[0].T,
+             "delayed rate as the true one": sr.motor_model(cmd.T, c.seen[0:12], c.seen[12:24], c.seen[12:24], kp=kp, kd=kd)[0].T}
+    some = np.nonzero(c.ok)[0][::5]                                           # every fifth kept env: the reference once more, under the wrong torque
+    for name, tau in wrong.items():
+        e = np.array([sr.vel_error(c.s1[sr.VEL_WORDS, g], c.again[g](tau[g])["v_next"]) for g in some])
+        print("   teeth, %s: a. reads %.1e (median), over the bound in %d of %d envs" % (name, np.median(e), (e > STEP_BOUNDS[c.thr]).sum(), len(some)))
+        # (1.3 ms: the rates move by a few tenths of a rad/s between the two blended entries; the delayed rate shows in about half the envs)
+        assert (e > STEP_BOUNDS[c.thr]).mean() >= 0.5 or (name != "undelayed" and latency[0] < 0.01)
