@@ -18,7 +18,7 @@ What tau has to be for the result to be the step's own forces: the step draws th
 (rex_motor_torque_params reproduces it) and the state holds no last torque, so the caller supplies tau; tau=None is zero torque."""
 import ctypes
 
-from . import _lib
+from . import _lib, readout
 
 # name -> (trailing shape after the row count, dtype name)
 FIELDS = {"toe_force": ((4, 2, 3), "float32"), "toe_lambda": ((4, 2, 3), "float32"), "limit_torque": ((12,), "float32"), "v_next": ((18,), "float32"),
@@ -31,16 +31,18 @@ def field_shape(name, k):
     return (k,) + FIELDS[name][0]
 
 
-class ContactSolve:
+class ContactSolve(readout.Result):
     """The result of RexBatchEnv.contact_solve: one tensor attribute per computed field (the others are None), `fields` their names, and
     `struct` the RexContactSolveOut the launch was given."""
+    WHO, FIELDS, STRUCT = "contact_solve", FIELDS, _lib.RexContactSolveOut
 
-    def __init__(self, tensors):
-        self.fields = tuple(n for n in FIELDS if n in tensors)
-        for n in FIELDS:
-            setattr(self, n, tensors.get(n))
-        self.struct = _lib.RexContactSolveOut(**{n: t.data_ptr() for n, t in tensors.items()})
-        self.rows = int(next(iter(tensors.values())).shape[0])
+    @classmethod
+    def shape_of(cls, name, k, env):
+        return field_shape(name, k)
+
+    @classmethod
+    def dtype_of(cls, name):
+        return FIELDS[name][1]
 
     @property
     def foot_force(self):
@@ -59,15 +61,7 @@ class ContactSolve:
 
 def check_fields(fields):
     """fields of RexBatchEnv.contact_solve -> their names in the order of FIELDS"""
-    if fields is None:
-        return tuple(FIELDS)
-    if isinstance(fields, str):
-        fields = (fields,)
-    fields = tuple(fields)
-    unknown = [f for f in fields if f not in FIELDS]
-    if unknown or not fields:
-        raise ValueError(f"contact_solve: fields must be a non-empty subset of {tuple(FIELDS)}, got {fields}")
-    return tuple(n for n in FIELDS if n in fields)
+    return readout.check_fields(FIELDS, "contact_solve", fields)
 
 
 def check_settings(dt, iterations, residual_threshold):
@@ -84,22 +78,13 @@ def check_settings(dt, iterations, residual_threshold):
 
 def check_result(out, names, k, env):
     """a result handed back through out=: its fields, shapes, dtypes, device"""
-    torch = env._torch
-    if not isinstance(out, ContactSolve) or out.fields != names:
-        raise ValueError(f"contact_solve: out must be a result of contact_solve() with the fields {names}")
-    for n in names:
-        t = getattr(out, n)
-        shape, dtype = field_shape(n, k), getattr(torch, FIELDS[n][1])
-        if not (isinstance(t, torch.Tensor) and t.dtype == dtype and t.device == env.device and tuple(t.shape) == shape and t.is_contiguous()
-                and t.data_ptr() == getattr(out.struct, n)):
-            raise ValueError(f"contact_solve: out.{n} must be the contiguous {FIELDS[n][1]} tensor of shape {shape} on {env.device} the result was made with")
+    readout.check_result(ContactSolve, out, names, k, env)
 
 
 def solve(env, tau=None, env_ids=None, fields=None, out=None, dt=None, iterations=None, residual_threshold=None, damping=True):
     """RexBatchEnv.contact_solve (documented there)."""
-    torch, who = env._torch, "contact_solve"
-    if env.mark == "arm":
-        raise NotImplementedError(f"{who}: mark 'arm' (24 degrees of freedom) is not supported")
+    who = "contact_solve"
+    readout.not_arm(env, who)
     if env.config.on_rack:
         raise ValueError(f"{who}: an on_rack env holds its base with an anchor the solve leaves out")
     if env.config.body_contacts:
@@ -108,19 +93,9 @@ def solve(env, tau=None, env_ids=None, fields=None, out=None, dt=None, iteration
     settings = check_settings(dt, iterations, residual_threshold)
     with env._on_stream():
         ids, k = env._row_ids(env_ids, who)
-        if tau is not None:
-            if not (isinstance(tau, torch.Tensor) and tau.dtype == torch.float32 and tau.device == env.device):
-                raise ValueError(f"{who}: tau must be a float32 tensor on {env.device}")
-            if tuple(tau.shape) == (12,):
-                tau = tau.expand(k, 12).contiguous()
-            if tuple(tau.shape) != (k, 12) or not tau.is_contiguous():
-                raise ValueError(f"{who}: tau must be contiguous with shape {(k, 12)} or (12,), got {tuple(tau.shape)}")
-        if out is None:
-            out = ContactSolve({n: torch.empty(field_shape(n, k), dtype=getattr(torch, FIELDS[n][1]), device=env.device) for n in names})
-        elif out is not env.__dict__.get("_contact_out") or out.fields != names or out.rows != k:
-            check_result(out, names, k, env)
-            env._contact_out = out
-        inp = _lib.RexContactSolveIn(tau.data_ptr() if tau is not None else None, settings[0], settings[1], settings[2], 1 if damping else 0)
-        _lib.check(env._L.rex_contact_solve(env._h, ids.data_ptr() if ids is not None else None, k, ctypes.byref(inp), ctypes.byref(out.struct),
-                                            env._stream_ptr()), "rex_contact_solve")
+        tau = None if tau is None else readout.load_tensor(env, tau, k, (12,), who, "tau")
+        out = readout.result(ContactSolve, env, out, names, k)
+        inp = _lib.RexContactSolveIn(readout.ptr(tau), settings[0], settings[1], settings[2], 1 if damping else 0)
+        _lib.check(env._L.rex_contact_solve(env._h, readout.ptr(ids), k, ctypes.byref(inp), ctypes.byref(out.struct), env._stream_ptr()),
+                   "rex_contact_solve")
     return out

@@ -287,7 +287,5 @@ __global__ void __launch_bounds__(kDynThreads) rex_contact_solve_kernel(DevCfg c
 }  // namespace rex
 
 hipError_t rex_launch_contact_solve(const RexSim* s, const int32_t* d_ids, int n, const rex::RexContactArgs& a, hipStream_t st) {
-  const int blocks = (n + rex::kDynEnvs - 1) / rex::kDynEnvs;
-  hipLaunchKernelGGL(rex::rex_contact_solve_kernel, dim3(blocks), dim3(rex::kDynThreads), rex::kDynFkBytes, st, s->dev, s->d_state, d_ids, n, a);
-  return hipGetLastError();
+  return rex::dyn_launch(rex::rex_contact_solve_kernel, rex::kDynFkBytes, s, d_ids, n, a, st);
 }

@@ -201,15 +201,13 @@ __global__ void __launch_bounds__(kDynThreads) rex_contact_space_kernel(DevCfg c
 __global__ void __launch_bounds__(kDynThreads) rex_inverse_dynamics_kernel(DevCfg c, const float* __restrict__ state, const int32_t* __restrict__ ids,
                                                                            int rows_total, RexInverseArgs a) {
   extern __shared__ __attribute__((aligned(16))) float s_inv[];
-  const int el = threadIdx.x >> 2, leg = threadIdx.x & 3;
-  const bool live = blockIdx.x * kDynEnvs + el < rows_total;
-  const int row = min(blockIdx.x * kDynEnvs + el, rows_total - 1);   // (the grid has ceil(rows_total / kDynEnvs) workgroups)
-  const int env = ids ? ids[row] : row;                              // the state's env index (checked on the host)
-  float (*R)[9] = reinterpret_cast<float (*)[9]>(s_inv + el * kDynStride);
-  float (*o)[3] = reinterpret_cast<float (*)[3]>(s_inv + el * kDynStride + 9 * REX_NB);
+  const DynLane T(ids, rows_total);
+  float (*R)[9] = reinterpret_cast<float (*)[9]>(s_inv + T.el * kDynStride);      // the row's tables in LDS
+  float (*o)[3] = reinterpret_cast<float (*)[3]>(s_inv + T.el * kDynStride + 9 * REX_NB);
+  const int leg = T.leg, row = T.row;
 
   DynFront F;
-  dyn_load_leg(c, state, env, leg, R, o, F);
+  dyn_load_leg(c, state, T.env, T.leg, R, o, F);
   const DynLeg& L = F.L;
 
   // ---- h(q, v) as rex_dynamics' bias ----
@@ -269,7 +267,7 @@ __global__ void __launch_bounds__(kDynThreads) rex_inverse_dynamics_kernel(DevCf
     bl = bl + mk(w[0], w[1], w[2]);
     bn = bn + mk(w[3], w[4], w[5]);
   }
-  if (live) {                                                // the lane's share, as rex_dynamics_solve_kernel stores a solution
+  if (T.live) {                                              // the lane's share, as rex_dynamics_solve_kernel stores a solution
     float* t = a.force + (size_t)row * kDynDof;
 #pragma unroll
     for (int i = 0; i < 3; ++i) t[6 + 3 * leg + i] = yf[i] - bf[i];
@@ -282,13 +280,9 @@ __global__ void __launch_bounds__(kDynThreads) rex_inverse_dynamics_kernel(DevCf
 }  // namespace rex
 
 hipError_t rex_launch_contact_space(const RexSim* s, const int32_t* d_ids, int n, const rex::RexContactSpaceArgs& a, hipStream_t st) {
-  const int blocks = (n + rex::kDynEnvs - 1) / rex::kDynEnvs;
-  hipLaunchKernelGGL(rex::rex_contact_space_kernel, dim3(blocks), dim3(rex::kDynThreads), rex::kDynFkBytes, st, s->dev, s->d_state, d_ids, n, a);
-  return hipGetLastError();
+  return rex::dyn_launch(rex::rex_contact_space_kernel, rex::kDynFkBytes, s, d_ids, n, a, st);
 }
 
 hipError_t rex_launch_inverse_dynamics(const RexSim* s, const int32_t* d_ids, int n, const rex::RexInverseArgs& a, hipStream_t st) {
-  const int blocks = (n + rex::kDynEnvs - 1) / rex::kDynEnvs;
-  hipLaunchKernelGGL(rex::rex_inverse_dynamics_kernel, dim3(blocks), dim3(rex::kDynThreads), rex::kDynFkBytes, st, s->dev, s->d_state, d_ids, n, a);
-  return hipGetLastError();
+  return rex::dyn_launch(rex::rex_inverse_dynamics_kernel, rex::kDynFkBytes, s, d_ids, n, a, st);
 }

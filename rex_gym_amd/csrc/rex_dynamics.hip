@@ -23,7 +23,8 @@
 // against 12.1 us for the full readout of 4 096 envs), unlike at the 1 KB per env of rex_kinematics.  The small outputs (bias,
 // gravity, com, momentum, mass) are stored by the lanes that hold them.  A null output pointer is a launch-uniform skip.  Lanes
 // of rows past the end repeat the last row, take part in the barriers and the quad sums, and store nothing to global memory.
-// Sections 1 and 2 live in rex_dynamics_leg.h, which rex_dynamics_solve.hip (the solves with M) includes too.
+// Sections 1 and 2, the lane mapping (DynLane) and section 3's bias (dyn_bias) live in rex_dynamics_leg.h, which rex_dynamics_solve.hip
+// (the solves with M) includes too.
 // (Built as part of rex_render.hip's object, like rex_kinematics.hip: rex_gym_amd/build.py INCLUDED_IN.)
 #include "rex_render_common.h"
 #include "rex_dynamics.h"
@@ -51,21 +52,19 @@ __device__ __forceinline__ void flush_rows(const float* lds, float* dst, int cou
 __global__ void __launch_bounds__(kDynThreads) rex_dynamics_kernel(DevCfg c, const float* __restrict__ state, const int32_t* __restrict__ ids,
                                                                    int rows_total, RexDynamicsOut out) {
   extern __shared__ __attribute__((aligned(16))) float s_dyn[];
-  const int el = threadIdx.x >> 2, leg = threadIdx.x & 3;
-  const bool live = blockIdx.x * kDynEnvs + el < rows_total;
-  const int row = min(blockIdx.x * kDynEnvs + el, rows_total - 1);   // (the grid has ceil(rows_total / kDynEnvs) workgroups)
-  const int env = ids ? ids[row] : row;                              // the state's env index (checked on the host)
+  const DynLane T(ids, rows_total);
+  float (*R)[9] = reinterpret_cast<float (*)[9]>(s_dyn + T.el * kDynStride);      // the row's tables in LDS
+  float (*o)[3] = reinterpret_cast<float (*)[3]>(s_dyn + T.el * kDynStride + 9 * REX_NB);
+  const int el = T.el, leg = T.leg, row = T.row;
+  const bool live = T.live;
   const int rows_live = min(kDynEnvs, rows_total - (int)blockIdx.x * kDynEnvs);   // this workgroup's rows of the output
-  float (*R)[9] = reinterpret_cast<float (*)[9]>(s_dyn + el * kDynStride);
-  float (*o)[3] = reinterpret_cast<float (*)[3]>(s_dyn + el * kDynStride + 9 * REX_NB);
 
   // ---- 1. the chain of this leg, 2. composites and the leg's blocks of M (rex_dynamics_leg.h) ----
   DynFront F;
-  dyn_load_leg(c, state, env, leg, R, o, F);
+  dyn_load_leg(c, state, T.env, T.leg, R, o, F);
   DynComposite C;
   dyn_composites(F, C);
-  const f3 o0 = F.o0, v0 = F.v0, w0 = F.w0, ofoot = F.ofoot, z3 = F.z3, aw = F.aw;
-  const Ground& g = F.g;
+  const f3 o0 = F.o0, v0 = F.v0, w0 = F.w0;
   const DynLeg& L = F.L;
   const s33& I0 = F.I0;
   const float m0 = F.m0, base = F.base, mt = C.mt;
@@ -121,13 +120,9 @@ __global__ void __launch_bounds__(kDynThreads) rex_dynamics_kernel(DevCfg c, con
     }
   }
   if (out.bias) {
-    f3 Fs[3], Ns[3];
-    leg_bias(L, w0, Fs, Ns);
+    f3 Ft, Nt;
     float tq[3];
-#pragma unroll
-    for (int i = 0; i < 3; ++i) tq[i] = dot(L.a[i], Ns[i] - cross(L.p[i], Fs[i]));
-    const f3 Ft = quad_sum(Fs[0] + (base * m0) * gz);                           // the base: a_c = 0, F = m g z, N = w x I w
-    const f3 Nt = quad_sum(Ns[0] + base * cross(w0, mul(I0, w0)));
+    dyn_bias(F, Ft, Nt, tq);
     if (live) {
       float* d = out.bias + (size_t)row * kDynDof;
       d[6 + 3 * leg] = tq[0]; d[7 + 3 * leg] = tq[1]; d[8 + 3 * leg] = tq[2];
@@ -159,11 +154,11 @@ __global__ void __launch_bounds__(kDynThreads) rex_dynamics_kernel(DevCfg c, con
   // ---- 5. the toe points of this leg and their Jacobians ----
   if (out.toe_jacobian) {
     __syncthreads();                                       // the FK tables, or the staged M, are dead
-    const f3 tc = toe_centre(ofoot, z3);
+    const f3 tc = toe_centre(F.ofoot, F.z3);
     const bool field = c.n_terrain > 0;
 #pragma unroll
     for (int e = 0; e < 2; ++e) {
-      const f3 d = toe_point(g, field, tc, aw, e).P - o0;
+      const f3 d = toe_point(F.g, field, tc, F.aw, e).P - o0;
       f3 col[3];
 #pragma unroll
       for (int i = 0; i < 3; ++i) col[i] = cross(L.a[i], d - L.p[i]);
@@ -191,7 +186,5 @@ __global__ void __launch_bounds__(kDynThreads) rex_dynamics_kernel(DevCfg c, con
 }  // namespace rex
 
 hipError_t rex_launch_dynamics(const RexSim* s, const int32_t* d_ids, int n, const RexDynamicsOut& out, hipStream_t st) {
-  const int blocks = (n + rex::kDynEnvs - 1) / rex::kDynEnvs;
-  hipLaunchKernelGGL(rex::rex_dynamics_kernel, dim3(blocks), dim3(rex::kDynThreads), rex::kDynLdsBytes, st, s->dev, s->d_state, d_ids, n, out);
-  return hipGetLastError();
+  return rex::dyn_launch(rex::rex_dynamics_kernel, rex::kDynLdsBytes, s, d_ids, n, out, st);
 }

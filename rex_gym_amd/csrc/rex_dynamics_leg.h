@@ -1,10 +1,12 @@
-// rex_dynamics_leg.h -- the front end that the kernels of the equations of motion share (rex_dynamics.hip, rex_dynamics_solve.hip, rex_contact_solve.hip):
+// rex_dynamics_leg.h -- the front end that the kernels of the equations of motion share (rex_dynamics.hip, rex_dynamics_solve.hip, rex_contact_solve.hip, rex_contact_space.hip):
 // one lane per (output row, leg) walks its leg's chain in LDS with the renderer's functions, holds the leg in registers (DynLeg),
 // forms the composite rigid bodies about the base origin o_0 and from them the leg's columns of the mass matrix -- the coupling
 // B_f (6 x 3, column i = (f_i, n_i)) and the leg block H_f (3 x 3) -- and, by DPP quad sums, the base block; leg_bias is the
 // Newton-Euler bias wrench.  Sections 1 and 2 of rex_dynamics_kernel, lifted with every expression spelled as it stood there
 // (the build fixes arithmetic by source, -ffp-contract=on: rex_dynamics' outputs are bit-identical to those before the lift,
 // profiles/dynamics_solve.md).  The formulation is described at the top of rex_dynamics.hip.
+// The lane mapping (DynLane), the bias projection h(q, v) (dyn_bias) and the launch (dyn_launch) are here once too, as far as the
+// kernels that use them still compile to the code they had (profiles/readout_refactor.md).
 #pragma once
 #include "rex_render_common.h"
 #include "rex_dynamics.h"
@@ -62,6 +64,20 @@ __device__ __forceinline__ void leg_bias(const DynLeg& L, f3 w0, f3* Fs, f3* Ns)
   Fs[1] = F[1] + Fs[2]; Ns[1] = N[1] + Ns[2];
   Fs[0] = F[0] + Fs[1]; Ns[0] = N[0] + Ns[1];
 }
+
+// ---- the lane: one per (output row, leg), a row's four legs one DPP quad, kDynEnvs rows per workgroup ----
+// (the pointers to the row's tables in LDS stay with the kernel: formed here and carried in the struct, they changed the kernels' code)
+struct DynLane {
+  int el, leg;             // row in the workgroup, leg
+  bool live;               // false on the lanes of rows past the end: they repeat the last row and store nothing
+  int row, env;            // output row; the state's env index (checked on the host)
+  __device__ __forceinline__ DynLane(const int32_t* ids, int rows_total) {
+    el = threadIdx.x >> 2; leg = threadIdx.x & 3;
+    live = blockIdx.x * kDynEnvs + el < rows_total;
+    row = min(blockIdx.x * kDynEnvs + el, rows_total - 1);   // (the grid has ceil(rows_total / kDynEnvs) workgroups)
+    env = ids ? ids[row] : row;
+  }
+};
 
 // ---- 1. the chain of this leg ----
 // what the lane holds of its row's env once the chain is walked
@@ -148,6 +164,28 @@ __device__ __forceinline__ void dyn_leg_block(const DynLeg& L, const DynComposit
   for (int i = 0; i < 3; ++i)
 #pragma unroll
     for (int j = 0; j <= i; ++j) H[i][j] = H[j][i] = dot(u[j], f[i]) + dot(L.a[j], nn[i]);
+}
+
+// ---- behind the front end: what the readouts agree on ----
+// h(q, v) as rex_dynamics' bias: the base rows Ft, Nt (about o_0; the quad's sum, on every lane) and the leg's rows
+// tq_i = a_i . (N_i - p_i x F_i), from leg_bias and the base body (a_c = 0, F = m g z, N = w x I w, on the leg-0 lane)
+__device__ __forceinline__ void dyn_bias(const DynFront& F, f3& Ft, f3& Nt, float (&tq)[3]) {
+  const DynLeg& L = F.L;
+  f3 Fs[3], Ns[3];
+  leg_bias(L, F.w0, Fs, Ns);
+  const f3 gz = mk(0.f, 0.f, kGravity);
+  Ft = quad_sum(Fs[0] + (F.base * F.m0) * gz);
+  Nt = quad_sum(Ns[0] + F.base * cross(F.w0, mul(F.I0, F.w0)));
+#pragma unroll
+  for (int i = 0; i < 3; ++i) tq[i] = dot(L.a[i], Ns[i] - cross(L.p[i], Fs[i]));
+}
+
+// one kernel of this mapping over n rows (row k = env ids[k], or env k with ids null) with lds_bytes of dynamic LDS
+template <typename Kernel, typename Args>
+hipError_t dyn_launch(Kernel kernel, int lds_bytes, const RexSim* s, const int32_t* ids, int n, const Args& args, hipStream_t st) {
+  const int blocks = (n + kDynEnvs - 1) / kDynEnvs;
+  hipLaunchKernelGGL(kernel, dim3(blocks), dim3(kDynThreads), lds_bytes, st, s->dev, s->d_state, ids, n, args);
+  return hipGetLastError();
 }
 
 }  // namespace

@@ -18,7 +18,7 @@
 //                  f_p at the lane's own two toe points (toe_point, rex_toe_point.h: the point rex_kinematics and rex_dynamics
 //                  report; the ground is queried only when toe forces are given), the base rows of J_p^T f_p = (f, (P - o_0) x f)
 //                  by quad sum, the leg rows col_i . f with col_i = a_i x (P - o_0 - p_i);  w the wrench at the base origin;
-//                  h from leg_bias exactly as rex_dynamics' bias.  x is vdot [n][18].
+//                  h by dyn_bias, which is rex_dynamics' bias.  x is vdot [n][18].
 //   kSolveImpulse  the same assembly without h, every input an impulse; x is dv [n][18] (or null), and the lanes add dv to the
 //                  velocity words of the row's env -- REX_S_LINVEL by the leg-0 lane, REX_S_ANGVEL by the leg-1 lane, the leg's
 //                  three REX_S_QD words by its own lane -- one fp32 add per word from the value the front end read; no other
@@ -46,16 +46,15 @@ __global__ void __launch_bounds__(kDynThreads) rex_dynamics_solve_kernel(DevCfg 
                                                                          int rows_total, RexSolveArgs a) {
   constexpr int NM = REX_NUM_MOTORS;
   extern __shared__ __attribute__((aligned(16))) float s_sol[];
-  const int el = threadIdx.x >> 2, leg = threadIdx.x & 3;
-  const bool live = blockIdx.x * kDynEnvs + el < rows_total;
-  const int row = min(blockIdx.x * kDynEnvs + el, rows_total - 1);   // (the grid has ceil(rows_total / kDynEnvs) workgroups)
-  const int env = ids ? ids[row] : row;                              // the state's env index (checked on the host)
-  float (*R)[9] = reinterpret_cast<float (*)[9]>(s_sol + el * kDynStride);
-  float (*o)[3] = reinterpret_cast<float (*)[3]>(s_sol + el * kDynStride + 9 * REX_NB);
+  const DynLane T(ids, rows_total);
+  float (*R)[9] = reinterpret_cast<float (*)[9]>(s_sol + T.el * kDynStride);      // the row's tables in LDS
+  float (*o)[3] = reinterpret_cast<float (*)[3]>(s_sol + T.el * kDynStride + 9 * REX_NB);
+  const int el = T.el, leg = T.leg, row = T.row, env = T.env;
+  const bool live = T.live;
 
   // ---- the leg, its composites, H_f and B_f, the base block (rex_dynamics_leg.h) ----
   DynFront F;
-  dyn_load_leg(c, state, env, leg, R, o, F);
+  dyn_load_leg(c, state, T.env, T.leg, R, o, F);
   DynComposite C;
   dyn_composites(F, C);
   const DynLeg& L = F.L;
@@ -66,8 +65,6 @@ __global__ void __launch_bounds__(kDynThreads) rex_dynamics_solve_kernel(DevCfg 
   DynFactor Q;
   dyn_factor(C, H, Q);
 
-  // x = M^-1 (b0, bf of every leg); x0 on every lane of the quad, xf the lane's own
-  auto solve = [&](const float (&b0)[6], const float (&bf)[3], float (&x0)[6], float (&xf)[3]) { dyn_msolve(Q, b0, bf, x0, xf); };
   // the lane's share of a solution: its leg's three joints; the base's linear part by the leg-0 lane, its angular part by the leg-1 lane
   auto store = [&](float* d, const float (&x0)[6], const float (&xf)[3]) {
     d[6 + 3 * leg] = xf[0]; d[7 + 3 * leg] = xf[1]; d[8 + 3 * leg] = xf[2];
@@ -87,7 +84,7 @@ __global__ void __launch_bounds__(kDynThreads) rex_dynamics_solve_kernel(DevCfg 
       const float b0[6] = {b[0], b[1], b[2], b[3], b[4], b[5]};
       const float bf[3] = {b[6 + 3 * leg], b[7 + 3 * leg], b[8 + 3 * leg]};
       float x0[6], xf[3];
-      solve(b0, bf, x0, xf);
+      dyn_msolve(Q, b0, bf, x0, xf);
       emit(a.x + (wg_row * (size_t)a.K + (size_t)k) * kDynDof, (size_t)a.K * kDynDof, x0, xf);
     }
     return;
@@ -121,21 +118,16 @@ __global__ void __launch_bounds__(kDynThreads) rex_dynamics_solve_kernel(DevCfg 
     bn = bn + mk(w[3], w[4], w[5]);
   }
   if (a.mode == kSolveForward) {                             // h as rex_dynamics' bias
-    f3 Fs[3], Ns[3];
-    leg_bias(L, F.w0, Fs, Ns);
-    const f3 gz = mk(0.f, 0.f, kGravity);
-    const f3 Ft = quad_sum(Fs[0] + (F.base * F.m0) * gz);
-    const f3 Nt = quad_sum(Ns[0] + F.base * cross(F.w0, mul(F.I0, F.w0)));
+    f3 Ft, Nt;
+    float tq[3];
+    dyn_bias(F, Ft, Nt, tq);
 #pragma unroll
-    for (int i = 0; i < 3; ++i) {
-      const float tq = dot(L.a[i], Ns[i] - cross(L.p[i], Fs[i]));
-      bf[i] -= tq;
-    }
+    for (int i = 0; i < 3; ++i) bf[i] -= tq[i];
     bl = bl - Ft; bn = bn - Nt;
   }
   const float b0[6] = {bl.x, bl.y, bl.z, bn.x, bn.y, bn.z};
   float x0[6], xf[3];
-  solve(b0, bf, x0, xf);
+  dyn_msolve(Q, b0, bf, x0, xf);
   if (a.x) emit(a.x + wg_row * kDynDof, kDynDof, x0, xf);
   if (a.state && live) {                                             // the push: v += dv, one add per word
     const int n = c.n;
@@ -158,7 +150,5 @@ __global__ void __launch_bounds__(kDynThreads) rex_dynamics_solve_kernel(DevCfg 
 }  // namespace rex
 
 hipError_t rex_launch_dynamics_solve(const RexSim* s, const int32_t* d_ids, int n, const rex::RexSolveArgs& a, hipStream_t st) {
-  const int blocks = (n + rex::kDynEnvs - 1) / rex::kDynEnvs;
-  hipLaunchKernelGGL(rex::rex_dynamics_solve_kernel, dim3(blocks), dim3(rex::kDynThreads), rex::kDynFkBytes, st, s->dev, s->d_state, d_ids, n, a);
-  return hipGetLastError();
+  return rex::dyn_launch(rex::rex_dynamics_solve_kernel, rex::kDynFkBytes, s, d_ids, n, a, st);
 }

@@ -1139,6 +1139,14 @@ int rex_num_bodies(const RexConfig* c) {
   return c->mark == REX_MARK_ARM ? REX_NB + REXA_NJ : REX_NB;
 }
 
+// the tail the readout entry points share: the sim's device, one launch over the rows (a macro, so that HIPCHK's message names the launcher)
+#define READOUT_LAUNCH(launcher, args)                            \
+  do {                                                            \
+    HIPCHK(hipSetDevice(s->device));                              \
+    HIPCHK(launcher(s, d_env_ids, n, args, (hipStream_t)stream)); \
+    return REX_OK;                                                \
+  } while (0)
+
 int rex_kinematics(RexSim* s, const int32_t* d_env_ids, int n, const RexKinematicsOut* out, void* stream) {
   const char* who = "rex_kinematics";
   if (!out) return failf(REX_EINVAL, "%s: null pointer", who);
@@ -1148,9 +1156,7 @@ int rex_kinematics(RexSim* s, const int32_t* d_env_ids, int n, const RexKinemati
   if (!out->link_pos && !out->link_quat && !out->link_linvel && !out->link_angvel && !out->toe_pos && !out->toe_vel && !out->toe_dist &&
       !out->toe_normal && !out->toe_in_reach && !out->base_body)
     return failf(REX_EINVAL, "%s: every output pointer is null", who);
-  HIPCHK(hipSetDevice(s->device));
-  HIPCHK(rex_launch_kinematics(s, d_env_ids, n, *out, (hipStream_t)stream));
-  return REX_OK;
+  READOUT_LAUNCH(rex_launch_kinematics, *out);
 }
 
 static_assert(sizeof(RexDynamicsOut) == 56, "RexDynamicsOut: 7 pointers, no padding (rex_gym_amd/_lib.py mirrors it)");
@@ -1166,9 +1172,7 @@ int rex_dynamics(RexSim* s, const int32_t* d_env_ids, int n, const RexDynamicsOu
     return failf(REX_EINVAL, "%s: every output pointer is null", who);
   if (((uintptr_t)out->mass_matrix | (uintptr_t)out->toe_jacobian) & 15u)   // (the kernel writes these two in 16-byte chunks)
     return failf(REX_EINVAL, "%s: mass_matrix and toe_jacobian must be 16-byte aligned", who);
-  HIPCHK(hipSetDevice(s->device));
-  HIPCHK(rex_launch_dynamics(s, d_env_ids, n, *out, (hipStream_t)stream));
-  return REX_OK;
+  READOUT_LAUNCH(rex_launch_dynamics, *out);
 }
 
 static_assert(sizeof(RexDynamicsLoad) == 24, "RexDynamicsLoad: 3 pointers, no padding (rex_gym_amd/_lib.py mirrors it)");
@@ -1193,9 +1197,7 @@ int rex_dynamics_solve(RexSim* s, const int32_t* d_env_ids, int n, int K, const 
   if (r0 != x0 && r0 < x0 + bytes && x0 < r0 + bytes)
     return failf(REX_EINVAL, "%s: d_rhs and d_x overlap in part (the same pointer solves in place; otherwise they must be disjoint)", who);
   rex::RexSolveArgs a{rex::kSolveRhs, K, d_rhs, d_x, nullptr, nullptr, nullptr, nullptr};
-  HIPCHK(hipSetDevice(s->device));
-  HIPCHK(rex_launch_dynamics_solve(s, d_env_ids, n, a, (hipStream_t)stream));
-  return REX_OK;
+  READOUT_LAUNCH(rex_launch_dynamics_solve, a);
 }
 
 int rex_forward_dynamics(RexSim* s, const int32_t* d_env_ids, int n, const RexDynamicsLoad* load, float* d_vdot, void* stream) {
@@ -1204,9 +1206,7 @@ int rex_forward_dynamics(RexSim* s, const int32_t* d_env_ids, int n, const RexDy
   const int rows_err = solve_rows(who, s, d_env_ids, n);
   if (rows_err != REX_OK) return rows_err;
   rex::RexSolveArgs a{rex::kSolveForward, 1, nullptr, d_vdot, load->joint, load->toe, load->base, nullptr};
-  HIPCHK(hipSetDevice(s->device));
-  HIPCHK(rex_launch_dynamics_solve(s, d_env_ids, n, a, (hipStream_t)stream));
-  return REX_OK;
+  READOUT_LAUNCH(rex_launch_dynamics_solve, a);
 }
 
 int rex_apply_impulse(RexSim* s, const int32_t* d_env_ids, int n, const RexDynamicsLoad* impulse, float* d_dv, void* stream) {
@@ -1217,9 +1217,7 @@ int rex_apply_impulse(RexSim* s, const int32_t* d_env_ids, int n, const RexDynam
   if (!impulse->joint && !impulse->toe && !impulse->base) return failf(REX_EINVAL, "%s: every impulse pointer is null", who);
   if (s->cfg.on_rack) return failf(REX_EINVAL, "%s: an on_rack sim holds its base with an anchor the solve leaves out", who);
   rex::RexSolveArgs a{rex::kSolveImpulse, 1, nullptr, d_dv, impulse->joint, impulse->toe, impulse->base, s->d_state};
-  HIPCHK(hipSetDevice(s->device));
-  HIPCHK(rex_launch_dynamics_solve(s, d_env_ids, n, a, (hipStream_t)stream));
-  return REX_OK;
+  READOUT_LAUNCH(rex_launch_dynamics_solve, a);
 }
 
 static_assert(sizeof(RexContactSolveIn) == 24 && sizeof(RexContactSolveOut) == 40, "RexContactSolveIn: a pointer, four 4-byte words; RexContactSolveOut: 5 pointers (rex_gym_amd/_lib.py mirrors them)");
@@ -1240,9 +1238,7 @@ int rex_contact_solve(RexSim* s, const int32_t* d_env_ids, int n, const RexConta
     return failf(REX_EINVAL, "%s: iterations %d: 1 .. %d", who, a.iterations, rex::kContactMaxIterations);
   if (!(a.dt > 0.0f) || !std::isfinite(a.dt) || !(a.threshold >= 0.0f) || !std::isfinite(a.threshold))
     return failf(REX_EINVAL, "%s: dt %g, residual_threshold %g: a finite dt > 0 and a finite threshold", who, (double)in->dt, (double)in->residual_threshold);
-  HIPCHK(hipSetDevice(s->device));
-  HIPCHK(rex_launch_contact_solve(s, d_env_ids, n, a, (hipStream_t)stream));
-  return REX_OK;
+  READOUT_LAUNCH(rex_launch_contact_solve, a);
 }
 
 static_assert(sizeof(RexContactSpaceOut) == 24, "RexContactSpaceOut: 3 pointers, no padding (rex_gym_amd/_lib.py mirrors it)");
@@ -1253,9 +1249,7 @@ int rex_inverse_dynamics(RexSim* s, const int32_t* d_env_ids, int n, const float
   const int rows_err = solve_rows(who, s, d_env_ids, n);
   if (rows_err != REX_OK) return rows_err;
   rex::RexInverseArgs a{d_vdot, load ? load->joint : nullptr, load ? load->toe : nullptr, load ? load->base : nullptr, d_force};
-  HIPCHK(hipSetDevice(s->device));
-  HIPCHK(rex_launch_inverse_dynamics(s, d_env_ids, n, a, (hipStream_t)stream));
-  return REX_OK;
+  READOUT_LAUNCH(rex_launch_inverse_dynamics, a);
 }
 
 int rex_contact_space(RexSim* s, const int32_t* d_env_ids, int n, const float* d_tau, const float* d_base_wrench, const RexContactSpaceOut* out,
@@ -1269,9 +1263,7 @@ int rex_contact_space(RexSim* s, const int32_t* d_env_ids, int n, const float* d
   if ((uintptr_t)out->delassus & 15u)                        // (the kernel writes it in 16-byte chunks)
     return failf(REX_EINVAL, "%s: delassus must be 16-byte aligned", who);
   rex::RexContactSpaceArgs a{d_tau, d_base_wrench, *out};
-  HIPCHK(hipSetDevice(s->device));
-  HIPCHK(rex_launch_contact_space(s, d_env_ids, n, a, (hipStream_t)stream));
-  return REX_OK;
+  READOUT_LAUNCH(rex_launch_contact_space, a);
 }
 
 int rex_ik_solve(int n, const float* d_orn, const float* d_pos, const float* d_frames, float* d_angles, void* stream) {

@@ -13,7 +13,7 @@ import ctypes
 import os
 import re
 
-from . import _lib
+from . import _lib, readout
 
 # name -> (trailing shape after the row count, with NB for the number of bodies; uint8?)
 FIELDS = {"link_pos": (("NB", 3), False), "link_quat": (("NB", 4), False), "link_linvel": (("NB", 3), False), "link_angvel": (("NB", 3), False),
@@ -39,16 +39,18 @@ def field_shape(name, k, num_bodies):
     return (k,) + tuple(num_bodies if d == "NB" else d for d in FIELDS[name][0])
 
 
-class Kinematics:
+class Kinematics(readout.Result):
     """The result of RexBatchEnv.kinematics: one tensor attribute per computed field (the others are None), `fields` their names,
     and `struct` the RexKinematicsOut the launch was given."""
+    WHO, FIELDS, STRUCT, DTYPE_SHOWN = "kinematics", FIELDS, _lib.RexKinematicsOut, "torch.%s"
 
-    def __init__(self, tensors):
-        self.fields = tuple(n for n in FIELDS if n in tensors)
-        for n in FIELDS:
-            setattr(self, n, tensors.get(n))
-        self.struct = _lib.RexKinematicsOut(**{n: t.data_ptr() for n, t in tensors.items()})
-        self.rows = int(next(iter(tensors.values())).shape[0])
+    @classmethod
+    def shape_of(cls, name, k, env):
+        return field_shape(name, k, env.num_bodies)
+
+    @classmethod
+    def dtype_of(cls, name):
+        return "uint8" if FIELDS[name][1] else "float32"
 
     @property
     def foot_clearance(self):
@@ -67,43 +69,19 @@ class Kinematics:
 
 def check_fields(fields):
     """fields of RexBatchEnv.kinematics -> their names in the order of FIELDS"""
-    if fields is None:
-        return tuple(FIELDS)
-    if isinstance(fields, str):
-        fields = (fields,)
-    fields = tuple(fields)
-    unknown = [f for f in fields if f not in FIELDS]
-    if unknown or not fields:
-        raise ValueError(f"kinematics: fields must be a non-empty subset of {tuple(FIELDS)}, got {fields}")
-    return tuple(n for n in FIELDS if n in fields)
+    return readout.check_fields(FIELDS, "kinematics", fields)
 
 
 def check_result(out, names, k, env):
     """a result handed back through out=: its fields, shapes, dtypes, device"""
-    torch = env._torch
-    if not isinstance(out, Kinematics) or out.fields != names:
-        raise ValueError(f"kinematics: out must be a result of kinematics() with the fields {names}")
-    for n in names:
-        t = getattr(out, n)
-        dtype = torch.uint8 if FIELDS[n][1] else torch.float32
-        shape = field_shape(n, k, env.num_bodies)
-        if not (isinstance(t, torch.Tensor) and t.dtype == dtype and t.device == env.device and tuple(t.shape) == shape and t.is_contiguous()
-                and t.data_ptr() == getattr(out.struct, n)):
-            raise ValueError(f"kinematics: out.{n} must be the contiguous {dtype} tensor of shape {shape} on {env.device} the result was made with")
+    readout.check_result(Kinematics, out, names, k, env)
 
 
 def read(env, env_ids=None, fields=None, out=None):
     """RexBatchEnv.kinematics (documented there)."""
-    torch = env._torch
     names = check_fields(fields)
     with env._on_stream():
         ids, k = env._row_ids(env_ids, "kinematics")
-        if out is None:
-            out = Kinematics({n: torch.empty(field_shape(n, k, env.num_bodies), dtype=torch.uint8 if FIELDS[n][1] else torch.float32, device=env.device)
-                              for n in names})
-        elif out is not env.__dict__.get("_kin_out") or out.fields != names or out.rows != k:
-            check_result(out, names, k, env)
-            env._kin_out = out
-        _lib.check(env._L.rex_kinematics(env._h, ids.data_ptr() if ids is not None else None, k, ctypes.byref(out.struct), env._stream_ptr()),
-                   "rex_kinematics")
+        out = readout.result(Kinematics, env, out, names, k)
+        _lib.check(env._L.rex_kinematics(env._h, readout.ptr(ids), k, ctypes.byref(out.struct), env._stream_ptr()), "rex_kinematics")
     return out

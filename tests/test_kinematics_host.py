@@ -153,3 +153,63 @@ def test_reference_alone_keeps_nine_tenths_of_the_points_and_covers_the_cases(me
         if n >= 67:
             tk.count_cases(tk.scene_reference(mark, n, ground, None), seen)
     tk.assert_cases_cover(seen)
+
+
+# ---------------------------------------------------------------- fields= and out= of the four readouts (rex_gym_amd/readout.py behind each module)
+# module name -> (the query's name in its messages, how a message shows float32, the fields that are not float32: how it shows their dtype)
+READOUTS = {"kinematics": ("kinematics", "torch.float32", {"toe_in_reach": "torch.uint8"}), "dynamics": ("dynamics", "float32", {}),
+            "contact": ("contact_solve", "float32", {"sweeps": "int32"}), "contact_space": ("contact_space", "float32", {})}
+
+
+def _readout(module):
+    """-> (the module, its result class, a stub env on the CPU, the shape of every field at 5 rows and 13 bodies)"""
+    import importlib
+    import torch
+    mod = importlib.import_module("rex_gym_amd." + module)
+    cls = next(v for v in vars(mod).values() if isinstance(v, type) and v.__module__ == mod.__name__)
+    env = type("StubEnv", (), dict(_torch=torch, device=torch.device("cpu"), num_bodies=13))()
+    shapes = {n: mod.field_shape(n, 5, 13) if module == "kinematics" else mod.field_shape(n, 5) for n in mod.FIELDS}
+    return mod, cls, env, shapes
+
+
+def _result(module):
+    import torch
+    mod, cls, env, shapes = _readout(module)
+    shown = READOUTS[module][2]
+    return cls({n: torch.zeros(shapes[n], dtype=getattr(torch, shown.get(n, "float32").split(".")[-1])) for n in mod.FIELDS})
+
+
+@pytest.mark.parametrize("module", list(READOUTS))
+def test_every_readout_refuses_bad_fields_and_results_with_its_own_messages(module):
+    """What check_fields and check_result of each of the four modules refuse, and the words they refuse it with: an unknown field, an empty
+    field list, a result of another query or of other fields, and per field a wrong dtype, a wrong row count and a tensor that is not the
+    one the struct points to."""
+    import torch
+    mod, cls, env, shapes = _readout(module)
+    who, f32, shown = READOUTS[module]
+    names = tuple(mod.FIELDS)
+    for bad in (("nope",), (names[0], "nope"), ()):
+        with pytest.raises(ValueError) as e:
+            mod.check_fields(bad)
+        assert str(e.value) == f"{who}: fields must be a non-empty subset of {names}, got {bad}"
+    out = _result(module)
+    assert out.fields == names and out.rows == 5 and mod.check_result(out, names, 5, env) is None
+    other = _result("dynamics" if module != "dynamics" else "contact_space")
+    for wrong, want in ((other, names), (out, names[:1]), (None, names)):
+        with pytest.raises(ValueError) as e:
+            mod.check_result(wrong, want, 5, env)
+        assert str(e.value) == f"{who}: out must be a result of {who}() with the fields {want}"
+    for n in names:
+        def refused(k):
+            with pytest.raises(ValueError) as e:
+                mod.check_result(out, names, k, env)
+            return str(e.value) == f"{who}: out.{n} must be the contiguous {shown.get(n, f32)} tensor of shape {(k,) + shapes[n][1:]} on cpu the result was made with"
+        good = getattr(out, n)
+        if n == names[0]:
+            assert refused(6)                                                      # the row count: the first field reports it
+        same_bytes = {torch.float32: torch.int32, torch.int32: torch.float32, torch.uint8: torch.int8}[good.dtype]
+        for bad in (good.view(same_bytes), good.clone(), None):                     # the dtype alone; another tensor; no tensor
+            setattr(out, n, bad)
+            assert refused(5), (n, bad)
+        setattr(out, n, good)
+    assert mod.check_result(out, names, 5, env) is None
