@@ -717,6 +717,58 @@ REX_API int rex_inverse_dynamics(RexSim* sim, const int32_t* d_env_ids, int n, c
 REX_API int rex_contact_space(RexSim* sim, const int32_t* d_env_ids, int n, const float* d_tau /* nullable */,
                               const float* d_base_wrench /* nullable */, const RexContactSpaceOut* out, void* stream);
 
+/* Force distribution (csrc/rex_force_distribution.h): which ground forces inside the friction cones produce a wanted acceleration, and
+ * which joint torques go with them -- a regularised cone-constrained least-squares problem per row, solved by a fixed number of
+ * accelerated projected-gradient steps in ONE read-only launch.  Mark base only.  Rows, ids and launch as rex_dynamics: no host sync; v,
+ * the order of its 18 components, M, h, J_p, the masses (with the env's scales) and the toe points p = 2 leg + e are rex_dynamics'.
+ * For one row, P_p are the eight toe points (rex_kinematics' toe_pos), n_p the ground normal there, o_0 the base origin, d_p = P_p - o_0.
+ *   Wanted base wrench   r = (M vdot + h - w)[0:6]: the six base rows of the equation of motion, the rows no motor supplies
+ *                        (rex_inverse_dynamics(vdot, base = w)[0:6]).  d_vdot NULL: zero ("hold still"); d_base_wrench NULL: zero.
+ *   The ground supplies  A f = (sum_p f_p, sum_p d_p x f_p): the base rows of sum_p J_p^T f_p.
+ *   Stance set S         d_stance [n][4], uint8, per LEG (both ends of its toe), nonzero = the leg may push.  NULL: every POINT in reach,
+ *                        dist < 0.02 m, rex_kinematics' toe_in_reach.
+ *   Cones                K_p = { f : |f - (n_p . f) n_p| <= mu_p (n_p . f) }, the circular Coulomb cone about the local normal, mu_p =
+ *                        friction_scale x the env's foot friction (the value rex_contact_solve uses).  It lies inside the step's friction
+ *                        pyramid: a force from here is one the simulated contact can hold.  f_p = 0 for p outside S.
+ *   Problem              minimise  1/2 (A f - r)^T W (A f - r) + 1/2 eps sum_p |f_p|^2   over f_p in K_p (p in S), f_p = 0 otherwise,
+ *                        W = diag(weights), weights > 0, eps > 0: strictly convex, one solution.  A has rank at most 6 against 24
+ *                        unknowns, so the regulariser is mandatory.  It biases the solution: even where r is reachable, A f falls short
+ *                        of it by a ridge shrinkage of the order eps / sigma_min(A)^2 (base_residual reports it).
+ *   Solver               accelerated projected gradient, constant scheme, exactly `iterations` steps from f = y = 0, no early exit:
+ *                          L = eps + sum_{p in S} [w_0 + w_1 + w_2 + w_3 (d_y^2 + d_z^2) + w_4 (d_x^2 + d_z^2) + w_5 (d_x^2 + d_y^2)]
+ *                          kappa = L / eps,  beta = (sqrt(kappa) - 1) / (sqrt(kappa) + 1);  each step
+ *                          u = W (A y - r);  g_p = u_lin + u_ang x d_p + eps y_p;  f+_p = Proj_Kp(y_p - g_p / L);
+ *                          y = f+ + beta (f+ - f);  f = f+
+ *                        Proj_K, with s = n . x and t = x - s n:  x if |t| <= mu s;  0 if mu |t| <= -s;  else s' n + mu s' t / |t| with
+ *                        s' = (s + mu |t|) / (1 + mu^2) (the tangential term is 0 when |t| = 0).  An empty S gives L = eps, f = 0.
+ *                        The caller judges convergence from `residual`.
+ * Outputs (any member may be NULL: not computed; each needs the alignment of a float):
+ *   toe_force     [n][4][2][3]  world N at toe_pos: f after the last step
+ *   tau           [n][12]       (M vdot + h)[6:18] - (sum_p J_p^T f_p)[6:18]: the joint torques that realise vdot under those forces.  Like
+ *                               `bias`, it holds no damping, joint-limit or motor terms
+ *   base_residual [n][6]        r - A f: the wrench the ground does not supply
+ *   residual      [n]           L max_p |Proj(f - g(f) / L) - f|_inf, N: the fixed-point residual at the returned f, the optimality measure
+ *                               (one more gradient evaluation)
+ * Not here: normal-force ceilings or floors, per-point weights, force tracking terms, a warm start.
+ * REX_EINVAL (message in rex_last_error) without a launch for: a null sim, params or out; n < 1; n > num_envs without ids; n * 24 >= 2^31;
+ * an `out` whose members are all NULL; a weight or eps that is not finite and positive; a friction_scale that is not finite or is
+ * negative; iterations outside 1 .. 10000; a sim of mark arm, on_rack or with body_contacts. */
+typedef struct RexForceDistributionParams {
+  float weights[6];            /* W: base force x, y, z, base moment x, y, z; each > 0 */
+  float eps;                   /* > 0 */
+  float friction_scale;        /* >= 0: mu_p = friction_scale x the env's foot friction */
+  int32_t iterations;          /* 1 .. 10000 */
+} RexForceDistributionParams;
+typedef struct RexForceDistributionOut {     /* any member may be NULL */
+  float* toe_force;            /* [n][4][2][3] */
+  float* tau;                  /* [n][12] */
+  float* base_residual;        /* [n][6] */
+  float* residual;             /* [n] */
+} RexForceDistributionOut;
+REX_API int rex_force_distribution(RexSim* sim, const int32_t* d_env_ids, int n, const float* d_vdot /* nullable */,
+                                   const float* d_base_wrench /* nullable */, const uint8_t* d_stance /* nullable */,
+                                   const RexForceDistributionParams* params, RexForceDistributionOut* out, void* stream);
+
 /* ---- the fused PPO learner (csrc/rex_learner.h): the losses of the reference's KL-penalty PPO (agents/ppo/algorithm.py:289-301,
  * 376-434) and their parameter gradients for a ForwardGaussianPolicy network (networks.py:69-112: obs_dim -> hidden1 -> hidden2 ->
  * out_dim, two ReLU layers), one pass over the episode memory per call.  Stateless: no RexSim, the library allocates nothing -- the

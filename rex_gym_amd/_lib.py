@@ -115,6 +115,17 @@ class RexContactSpaceOut(ctypes.Structure):
     _fields_ = [("delassus", ctypes.c_void_p), ("toe_drift", ctypes.c_void_p), ("toe_acc_free", ctypes.c_void_p)]
 
 
+class RexForceDistributionParams(ctypes.Structure):
+    """Mirror of `struct RexForceDistributionParams` (include/rexsim.h): the weights, the regulariser, the friction scale and the step
+    count of rex_force_distribution."""
+    _fields_ = [("weights", ctypes.c_float * 6), ("eps", ctypes.c_float), ("friction_scale", ctypes.c_float), ("iterations", ctypes.c_int32)]
+
+
+class RexForceDistributionOut(ctypes.Structure):
+    """Mirror of `struct RexForceDistributionOut` (include/rexsim.h): the device arrays rex_force_distribution fills (a null one is skipped)."""
+    _fields_ = [("toe_force", ctypes.c_void_p), ("tau", ctypes.c_void_p), ("base_residual", ctypes.c_void_p), ("residual", ctypes.c_void_p)]
+
+
 class RexPpoNet(ctypes.Structure):
     """Mirror of `struct RexPpoNet` (include/rexsim.h): a two-layer ReLU network of the fused learner, torch layout."""
     _fields_ = [("obs_dim", ctypes.c_int32), ("out_dim", ctypes.c_int32), ("hidden1", ctypes.c_int32), ("hidden2", ctypes.c_int32),
@@ -222,6 +233,8 @@ _SIGS = {
                               ctypes.c_void_p], ctypes.c_int),
     "rex_contact_space": ([ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(RexContactSpaceOut),
                            ctypes.c_void_p], ctypes.c_int),
+    "rex_force_distribution": ([ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                ctypes.POINTER(RexForceDistributionParams), ctypes.POINTER(RexForceDistributionOut), ctypes.c_void_p], ctypes.c_int),
     "rex_ppo_workspace_bytes": ([ctypes.c_int] * 6, ctypes.c_longlong),
     "rex_ppo_returns": ([ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_float, ctypes.c_void_p, ctypes.c_void_p,
                          ctypes.c_float, ctypes.c_void_p, ctypes.c_void_p], ctypes.c_int),

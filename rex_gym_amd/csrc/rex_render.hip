@@ -139,3 +139,5 @@ hipError_t rex_launch_render(const RexSim* s, const rex::RenderCam& cam, const i
 #include "rex_contact_solve.hip"
 // the acceleration level (rex_contact_space, rex_inverse_dynamics): the same front end and factors, the toe points' Delassus matrix
 #include "rex_contact_space.hip"
+// force distribution (rex_force_distribution): the same front end, then a fixed-length projected-gradient solve over the toe forces
+#include "rex_force_distribution.hip"

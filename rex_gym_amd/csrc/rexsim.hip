@@ -14,6 +14,7 @@
 #include "rex_dynamics_solve.h"
 #include "rex_contact_solve.h"
 #include "rex_contact_space.h"
+#include "rex_force_distribution.h"
 #include "rex_visual_gen.h"
 #include "rex_error.h"
 #include <algorithm>
@@ -1264,6 +1265,33 @@ int rex_contact_space(RexSim* s, const int32_t* d_env_ids, int n, const float* d
     return failf(REX_EINVAL, "%s: delassus must be 16-byte aligned", who);
   rex::RexContactSpaceArgs a{d_tau, d_base_wrench, *out};
   READOUT_LAUNCH(rex_launch_contact_space, a);
+}
+
+static_assert(sizeof(RexForceDistributionParams) == 36 && sizeof(RexForceDistributionOut) == 32,
+              "RexForceDistributionParams: nine 4-byte words; RexForceDistributionOut: 4 pointers (rex_gym_amd/_lib.py mirrors them)");
+
+int rex_force_distribution(RexSim* s, const int32_t* d_env_ids, int n, const float* d_vdot, const float* d_base_wrench, const uint8_t* d_stance,
+                           const RexForceDistributionParams* params, RexForceDistributionOut* out, void* stream) {
+  const char* who = "rex_force_distribution";
+  if (!params || !out) return failf(REX_EINVAL, "%s: null pointer", who);
+  const int rows_err = solve_rows(who, s, d_env_ids, n);
+  if (rows_err != REX_OK) return rows_err;
+  if ((long long)n * 24 >= (1ll << 31)) return failf(REX_EINVAL, "%s: n %d: n * 24 must stay below 2^31", who, n);
+  if (s->cfg.on_rack) return failf(REX_EINVAL, "%s: an on_rack sim holds its base with an anchor the problem leaves out", who);
+  if (s->cfg.body_contacts) return failf(REX_EINVAL, "%s: a sim with body_contacts pushes with link boxes the problem leaves out", who);
+  if (!out->toe_force && !out->tau && !out->base_residual && !out->residual) return failf(REX_EINVAL, "%s: every output pointer is null", who);
+  for (int i = 0; i < 6; ++i)
+    if (!(params->weights[i] > 0.0f) || !std::isfinite(params->weights[i]))
+      return failf(REX_EINVAL, "%s: weights[%d] %g: every weight must be finite and positive", who, i, (double)params->weights[i]);
+  if (!(params->eps > 0.0f) || !std::isfinite(params->eps))
+    return failf(REX_EINVAL, "%s: eps %g: the regulariser must be finite and positive (the problem has 24 unknowns and at most 6 equations)", who, (double)params->eps);
+  if (!(params->friction_scale >= 0.0f) || !std::isfinite(params->friction_scale))
+    return failf(REX_EINVAL, "%s: friction_scale %g: finite and not negative", who, (double)params->friction_scale);
+  if (params->iterations < 1 || params->iterations > rex::kForceMaxIterations)
+    return failf(REX_EINVAL, "%s: iterations %d: 1 .. %d", who, params->iterations, rex::kForceMaxIterations);
+  rex::RexForceArgs a{d_vdot, d_base_wrench, d_stance, {}, params->eps, params->friction_scale, params->iterations, *out};
+  for (int i = 0; i < 6; ++i) a.w[i] = params->weights[i];
+  READOUT_LAUNCH(rex_launch_force_distribution, a);
 }
 
 int rex_ik_solve(int n, const float* d_orn, const float* d_pos, const float* d_frames, float* d_angles, void* stream) {
