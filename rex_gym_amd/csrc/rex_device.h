@@ -1032,10 +1032,19 @@ __device__ long long g_prof2[16 * 1024]; // per block: inside pgs_dv: [0] set-up
                                          // inside the sweeps: [8] link-box rows run, [9] joint-limit rows run, cycles of [10] the limit rows,
                                          // [11] link-box normals, [12] toe rows, [13] link-box friction rows, [14] sweeps of thread 0's env
                                          // (what [8]-[13] cover)
+__device__ long long g_prof3[48 * 1024]; // per block, per WAVE sweep (whatever thread 0's env does): [k] cycles and [17 + k] number of the sweeps that
+                                         // began with k envs of the wave still running (k = 1..16); [34] sweeps that took the out-of-line residual
+                                         // block (REX_RESIDUAL_ON_DEMAND); [35 + c] sweeps in which candidate certificate set c (REX_PROF_CERT_SETS)
+                                         // would have taken it
 __device__ unsigned g_legmask[65536];   // per env: bits 0-7 the toe points in reach in the last substep, bits 8-15 their OR since the last read-out
 #define REX_STAMP(var) const long long var = clock64()
+/* -DREX_PROF_CERT_SETS=m0,m1,...,m11 on top (a build of its own: it adds work to every sweep; tools/prof_sections.py --cert holds the list):
+   12 candidate certificate sets, bit r = toe row r -- rows 0-7 the normals of points 2 L, 2 L + 1 of leg L, rows 8 + 2 k, 9 + 2 k the
+   friction pair of point k */
+#define REX_PROF_COUNT_ON_DEMAND() prof_took = true   /* (counted behind the sweep, where the other counters are: no store inside the block) */
 #else
 #define REX_STAMP(var)
+#define REX_PROF_COUNT_ON_DEMAND()
 #endif
 // per-variant code shape of the sweep loop (pgs_dv), chosen by measurement (tools/ab_libs.sh)
 /* mark 'arm' at 16 envs per wave (every register taken, 300-600 B of scratch): the row keeps invd * target and the sweep
@@ -1063,6 +1072,24 @@ __device__ unsigned g_legmask[65536];   // per env: bits 0-7 the toe points in r
 #endif
 #ifndef REX_PAIRED_SWEEPS
 #define REX_PAIRED_SWEEPS(EPW, ARM, BODY, MIXED) (!(BODY) && !(MIXED) && ((EPW) <= 8 || !(ARM)))
+#endif
+/* the velocity residual of the toe rows formed on demand (pgs_dv): `worst` is only ever compared with 0, and one row with
+   |dl| > thr invd settles that in every sweep of an env but its last.  Inside the pipelined block only the CERTIFICATE rows
+   (REX_CERT_ROW_MASK, bit r = toe row r) form their term; where they leave a running env undecided, one wave-uniform branch
+   behind the block forms the terms of the other rows from the two impulse sets -- lo[r] - li[r] is the subtraction row r made,
+   bit for bit, so `running` is the truth value it always was.  Needs the two sets, hence the paired sweeps only; the in-place
+   variants cannot recompute dl and keep the term in the row.  So do the TRACE instantiations (physics_substep passes INROW):
+   debug kernels whose speed does not matter, and whose bit-identity with the product kernels (tests/test_gpu_parity.py; trace
+   word [1] chains lane_sweeps) thereby checks on-demand against in-row, sweep counts included. */
+#ifndef REX_RESIDUAL_ON_DEMAND
+#define REX_RESIDUAL_ON_DEMAND(EPW, ARM, BODY, MIXED) REX_PAIRED_SWEEPS(EPW, ARM, BODY, MIXED)
+#endif
+/* one normal row per leg (an unloaded row has dl = 0 and certifies nothing): toe point 0 of the legs 0 and 2, point 1 of the legs 1
+   and 3 -- of the candidate sets of at most 6 rows the one with the fewest residual instructions per sweep on the bench's mix: the out-of-line
+   block runs in 20.7 % of the wave sweeps at 4 envs per wave (22.3 % in the waves that end a launch); with the first point of every
+   leg (0x55) in 79.1 % (tools/prof_sections.py --stagger --cert, profiles/residual_on_demand.md) */
+#ifndef REX_CERT_ROW_MASK
+#define REX_CERT_ROW_MASK 0x99u
 #endif
 __device__ __forceinline__ constexpr int crow_leg(int r) { return r < REX_NPOINT ? r / 2 : (r - REX_NPOINT) / 4; }
 __device__ __forceinline__ int crow_leg_rt(int r) { return r < REX_NPOINT ? r >> 1 : (r - REX_NPOINT) >> 2; }   // (a lane's own row index)
@@ -1144,13 +1171,15 @@ __device__ __forceinline__ void solve_run(const RunHead<NY>& head, const LOAD& l
 
 // `cpl_free`: called once the couplings have been read into registers -- their six LDS chunks are idle until the next
 // substep's row finishing, and physics_substep parks bystanders of the sweep loop there where registers are short
-template <int LPE, bool LANECAP, class SM, class ARMP, class F>
+template <int LPE, bool LANECAP, bool INROW, class SM, class ARMP, class F>
 __device__ __forceinline__ void pgs_dv(const SM& sm, ARMP& armp, PgsX& x, int p, const bool (&lim)[4], bool any_contact,
                                        unsigned bgroups, float mu, int iterations, int lane_iterations, float thr, int& nsweeps, int& lane_sweeps,
                                        const F& cpl_free) {
   constexpr int EPW = SM::kEpw, NY = (6 + LPE - 1) / LPE;
   constexpr int kRow = REX_ROW_F4 * EPW * 16;   // bytes from a row to the next
   constexpr bool kPairedSweeps = REX_PAIRED_SWEEPS(EPW, ARMP::NM > 12, SM::kBody, LANECAP);
+  constexpr bool kOnDemand = !INROW && REX_RESIDUAL_ON_DEMAND(EPW, ARMP::NM > 12, SM::kBody, LANECAP);   // the toe rows' residual (at the macro)
+  static_assert(!kOnDemand || kPairedSweeps, "residual on demand: lo[r] - li[r] needs the two impulse sets");
   REX_STAMP(t_dv0);
   DvLane<NY, EPW> ln;   // toe rows: the lanes without a component read the zero in word 11
   DvLane<NY, EPW> lr;   // LDS-resident rows (joint limits, link boxes): zero word 9, (tgt, invd) in words 10-11
@@ -1246,6 +1275,11 @@ __device__ __forceinline__ void pgs_dv(const SM& sm, ARMP& armp, PgsX& x, int p,
     // (`worst` lives outside the lane mask: a lane that has stopped keeps 0, and `running` is then one compare under the full EXEC --
     //  the wave's exit test reads that very mask instead of rebuilding a full-wave vote from a partial one)
     float worst = 0.0f;
+#ifdef REX_PROF
+    const int prof_nrun = __builtin_popcountll(__builtin_amdgcn_ballot_w64(running)) / (64 / EPW);   // envs of the wave that run this sweep
+    bool prof_took = false;
+    const long long t_w0 = clock64();
+#endif
     if (running) {
       ++lane_sweeps;
       REX_STAMP(t_s0);
@@ -1334,6 +1368,9 @@ __device__ __forceinline__ void pgs_dv(const SM& sm, ARMP& armp, PgsX& x, int p,
       if constexpr (SM::kBody) {
         if (bgroups != 0) { hf.a = body_load(REX_NBSLOT, false); hf.b = body_load(REX_NBSLOT + 1, false); prefetch_fence(); }
       }
+#ifdef REX_PROF_CERT_SETS
+      const float worst_pre = worst;
+#endif
       if (any_contact) {
         // contact rows, pipelined; this lane's slice of the rows sits in registers (Jy, Jz, Kc, Ki)
         float S, dlp = 0.0f;
@@ -1360,12 +1397,36 @@ __device__ __forceinline__ void pgs_dv(const SM& sm, ARMP& armp, PgsX& x, int p,
             for (int i = 0; i < NY; ++i) part = fmaf(Jy[r + 1][i], ys[i], part);
             S = group_sum<LPE>(part);
           }
-          worst = fmaxf(worst, fmaf(-thr, Ki[r], fabsf(dl)));   // |dl| / invd > thr: Bullet's velocity residual
+          if (!kOnDemand || ((REX_CERT_ROW_MASK >> r) & 1u)) worst = fmaxf(worst, fmaf(-thr, Ki[r], fabsf(dl)));   // |dl| / invd > thr: Bullet's velocity residual
           lo[r] = nl;
           dlp = dl;
 #pragma unroll
           for (int i = 0; i < NY; ++i) ys[i] = fmaf(Jy[r][i], dl, ys[i]);
           zs[L] = fmaf(Jz[r], dl, zs[L]);
+        }
+#ifdef REX_PROF_CERT_SETS
+        if constexpr (kOnDemand) {   // which certificate set: the sweeps in which each candidate would have taken the out-of-line block
+          constexpr unsigned sets[12] = {REX_PROF_CERT_SETS};
+#pragma unroll
+          for (int c = 0; c < 12; ++c) {
+            float w = worst_pre;
+#pragma unroll
+            for (int r = 0; r < REX_NCROW; ++r)
+              if ((sets[c] >> r) & 1u) w = fmaxf(w, fmaf(-thr, Ki[r], fabsf(lo[r] - li[r])));
+            const bool taken = __builtin_amdgcn_ballot_w64(!(w > 0.0f)) != 0;
+            if (taken && (int)threadIdx.x == __builtin_amdgcn_readfirstlane((int)threadIdx.x) && blockIdx.x < 1024) g_prof3[48 * blockIdx.x + 35 + c] += 1;
+          }
+        }
+#endif
+        if constexpr (kOnDemand) {
+          // the certificate rows left a running env undecided (its last sweep, or none of them loaded): the other rows' terms,
+          // out of line; every lane may run it, only the undecided lanes' values matter
+          if (__builtin_expect(__builtin_amdgcn_ballot_w64(!(worst > 0.0f)) != 0, 0)) {
+            REX_PROF_COUNT_ON_DEMAND();
+#pragma unroll
+            for (int r = 0; r < REX_NCROW; ++r)
+              if (!((REX_CERT_ROW_MASK >> r) & 1u)) worst = fmaxf(worst, fmaf(-thr, Ki[r], fabsf(lo[r] - li[r])));
+          }
         }
       }
       REX_STAMP(t_s3);
@@ -1413,6 +1474,14 @@ __device__ __forceinline__ void pgs_dv(const SM& sm, ARMP& armp, PgsX& x, int p,
     }             // (a lane that has stopped never sweeps again: what it leaves in `lo` is never read)
     // (the per-lane cap is compiled in for mixed-task batches only)
     running = LANECAP ? (worst > 0.0f && it + 1 < lane_iterations) : worst > 0.0f;
+#ifdef REX_PROF
+    const bool prof_wave_took = __builtin_amdgcn_ballot_w64(prof_took) != 0;   // (under the full EXEC: any env of the wave)
+    if (threadIdx.x == 0 && blockIdx.x < 1024) {
+      long long* p3 = g_prof3 + 48 * blockIdx.x;
+      p3[prof_nrun] += clock64() - t_w0; p3[17 + prof_nrun] += 1;
+      p3[34] += prof_wave_took;
+    }
+#endif
   };
   if constexpr (kPairedSweeps) {
     float lamB[REX_NCROW];
@@ -1869,7 +1938,7 @@ __device__ __forceinline__ void physics_substep(PhysState& s, float* tau, float 
         sm.parkf(REX_PARK_CPL + 3, 0) = s.q[17];
       }
     };
-    pgs_dv<LPE, LANECAP>(sm, armp, x, pl, lim, any0 || any1 || any2 || any3, bgroups, ground.mu, iterations, lane_iterations, sqrt_res_thr, nsweeps, lane_sweeps, park_body);
+    pgs_dv<LPE, LANECAP, TRACE>(sm, armp, x, pl, lim, any0 || any1 || any2 || any3, bgroups, ground.mu, iterations, lane_iterations, sqrt_res_thr, nsweeps, lane_sweeps, park_body);
     if constexpr (kRowParkBody) {
       const float4 a = sm.park(REX_PARK_CPL + 0), b = sm.park(REX_PARK_CPL + 1), c = sm.park(REX_PARK_CPL + 2);
       s.pos[0] = a.x; s.pos[1] = a.y; s.pos[2] = a.z; s.quat[0] = a.w; s.quat[1] = b.x; s.quat[2] = b.y; s.quat[3] = b.z; s.q[12] = b.w;

@@ -1344,6 +1344,11 @@ REX_API int rex_debug_prof2(long long* out, int reset) {   /* the sections of th
   if (reset) { static long long z[16 * 1024]; if (hipMemcpyToSymbol(HIP_SYMBOL(rex::g_prof2), z, sizeof(z)) != hipSuccess) return REX_EHIP; }
   return REX_OK;
 }
+REX_API int rex_debug_prof3(long long* out, int reset) {   /* per wave sweep: cycles by envs still running, out-of-line residual blocks taken */
+  if (out && hipMemcpyFromSymbol(out, HIP_SYMBOL(rex::g_prof3), sizeof(long long) * 48 * 1024) != hipSuccess) return REX_EHIP;
+  if (reset) { static long long z[48 * 1024]; if (hipMemcpyToSymbol(HIP_SYMBOL(rex::g_prof3), z, sizeof(z)) != hipSuccess) return REX_EHIP; }
+  return REX_OK;
+}
 #endif
 }  // extern "C"
 

@@ -98,4 +98,8 @@ for g in groups:
 #  group are exact under it.  The list is for review after a source change: a cross-lane instruction under a mask that is NOT
 #  uniform per lane group is the round-3 bug.)
 print("total cross-lane instructions under a narrowed EXEC (review list, not an error):", bad_cross)
+# the rows whose residual term the paired-sweep kernels form inside the toe-row block (rex_device.h REX_RESIDUAL_ON_DEMAND; read by
+# tests/test_isa_residual.py: the one place the count comes from)
+cert = int(re.search(r"^#define REX_CERT_ROW_MASK\s+(0x[0-9A-Fa-f]+)u?\s*$", open(os.path.join(CSRC, "rex_device.h")).read(), re.M).group(1), 16)
+print(f"certificate rows of the toe-row block: {bin(cert).count('1')} (REX_CERT_ROW_MASK {cert:#x})")
 sys.exit(1 if bad else 0)

@@ -4,7 +4,12 @@
 Builds the library with -DREX_PROF (clock64() stamps around the sections of physics_substep, accumulated per
 workgroup by lane 0) into scratch/librexsim_prof.so, runs walk-IK at N envs and prints cycles per substep for:
 leg factorisation, base Cholesky, row finishing, PGS sweeps, back-substitution + integration.
-  python tools/prof_sections.py [N=4096] [--arm] [--task=standup|poses|...] [--roll=R] [--body=0|1] [--rebuild]
+  python tools/prof_sections.py [N=4096] [--arm] [--task=standup|poses|...] [--roll=R] [--body=0|1] [--rebuild] [--stagger] [--cert]
+--stagger: the pre-roll of bench.py -- a random 1 / 32 of the batch reset every 50 of the first 1 300 pre-roll steps -- instead of a
+           synchronised batch: the stationary episode-age mix of the headline, with freshly reset (capped) envs in it
+--cert:    which certificate rows for the residual on demand (csrc/rex_device.h REX_CERT_ROW_MASK): a library of its own, built with
+           -DREX_PROF_CERT_SETS=<CERT_SETS below> (scratch/librexsim_prof_cert.so, or REX_PROF_LIB=...), counts per candidate set the WAVE
+           sweeps in which the out-of-line block would have run -- some running env of the wave left undecided
 """
 import ctypes
 import os
@@ -15,11 +20,16 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-so = os.environ.get("REX_PROF_LIB") or os.path.join(ROOT, "scratch", "librexsim_prof.so")   # REX_PROF_LIB: a prebuilt -DREX_PROF library (A/B)
+# the candidate certificate sets of --cert, bit r = toe row r (rows 0-7: the normals of points 2 L, 2 L + 1 of leg L; rows 8 + 2 k, 9 + 2 k: the
+# friction pair of point k); 12 of them (g_prof3[35..46]).  The one list: the library gets it as a define.
+CERT_SETS = [0x55, 0xAA, 0x99, 0x66, 0x9D, 0xBD, 0x9F, 0x3F, 0x90, 0x91, 0x4199, 0x410099]
+CERT = "--cert" in sys.argv
+so = os.environ.get("REX_PROF_LIB") or os.path.join(ROOT, "scratch", "librexsim_prof_cert.so" if CERT else "librexsim_prof.so")   # REX_PROF_LIB: a prebuilt library (A/B)
 os.makedirs(os.path.dirname(so), exist_ok=True)
 import rex_gym_amd.build as b
 if not os.path.exists(so) or "--rebuild" in sys.argv:
-    b.build(force=True, lib_path=so, defines=["-DREX_PROF"], unity=True)   # one translation unit: the counters are one device global
+    b.build(force=True, lib_path=so, defines=["-DREX_PROF"] + (["-DREX_PROF_CERT_SETS=" + ",".join("%#xu" % m for m in CERT_SETS)] if CERT else []),
+            unity=True)   # one translation unit: the counters are one device global
 b.LIB_PATH = so
 import torch
 from rex_gym_amd import RexBatchEnv, _lib
@@ -27,6 +37,10 @@ from rex_gym_amd import RexBatchEnv, _lib
 L = _lib.lib()
 L.rex_debug_prof.argtypes = [ctypes.c_void_p, ctypes.c_int]
 L.rex_debug_prof2.argtypes = [ctypes.c_void_p, ctypes.c_int]
+HAVE_PROF3 = hasattr(L, "rex_debug_prof3")      # (a -DREX_PROF library of a commit before the residual on demand has none: A/B runs)
+if HAVE_PROF3:
+    L.rex_debug_prof3.argtypes = [ctypes.c_void_p, ctypes.c_int]
+STAGGER = "--stagger" in sys.argv
 args = [a for a in sys.argv[1:] if not a.startswith("--")]
 n = int(args[0]) if args else 4096
 mark = "arm" if "--arm" in sys.argv else "base"
@@ -48,6 +62,8 @@ def window(steps, label):
     torch.cuda.synchronize()
     L.rex_debug_prof(None, 1)
     L.rex_debug_prof2(None, 1)
+    if HAVE_PROF3:
+        L.rex_debug_prof3(None, 1)
     for k in range(steps):
         env.step(acts[k % 8])
     torch.cuda.synchronize()
@@ -55,6 +71,11 @@ def window(steps, label):
     L.rex_debug_prof(out.ctypes.data, 0)
     out2 = np.zeros((1024, 16), np.int64)
     L.rex_debug_prof2(out2.ctypes.data, 0)
+    out3 = np.zeros((1024, 48), np.int64)
+    if HAVE_PROF3:
+        L.rex_debug_prof3(out3.ctypes.data, 0)
+    keep = out[:, 4] > 0
+    out3 = out3[keep].astype(float)
     out2 = out2[out[:, 4] > 0].astype(float)
     out = out[out[:, 4] > 0].astype(float)
     pgs, sw, tot, fin, sub, legs, chol = (out[:, i] for i in (0, 1, 2, 3, 4, 6, 7))
@@ -98,9 +119,34 @@ def window(steps, label):
         ca = out2[:, 10:14].sum(0) / nsa
         print("    all workgroups, per sweep: %.1f link-box rows + %.1f joint-limit rows; cycles: limit rows %.0f, link-box normals %.0f, toe rows %.0f, "
               "link-box friction %.0f" % (out2[:, 8].sum() / nsa, out2[:, 9].sum() / nsa, ca[0], ca[1], ca[2], ca[3]))
+    if out3[:, 17:34].sum() > 0:
+        # per WAVE sweep (whatever thread 0's env does), binned by the envs of the wave that still ran when the sweep began: does the
+        # `if (running)` lane mask cost a partly stopped wave anything?
+        cyc, cnt = out3[:, 0:17].sum(0), out3[:, 17:34].sum(0)
+        nsw = cnt.sum()
+        print("  wave sweeps %.0f, %.0f cycles each; by envs still running: " % (nsw, cyc.sum() / nsw) +
+              ", ".join("%d: %.0f cycles (%.1f %%)" % (k, cyc[k] / cnt[k], 100 * cnt[k] / nsw) for k in range(17) if cnt[k] > 0))
+        taken = out3[:, 34]
+        wsw = out3[:, 17:34].sum(1)
+        print("  out-of-line residual block: taken in %.2f %% of the wave sweeps (all workgroups), %.2f %% in the slowest workgroup "
+              "(%.1f wave sweeps/substep there)" % (100 * taken.sum() / nsw, 100 * taken[w] / max(wsw[w], 1), wsw[w] / sub[w]))
+        if CERT:
+            # mean instructions of the residual per wave sweep = 1.5 per certificate row in the block (fma + half a max3) + taken share x
+            # 2.5 per other row out of line (sub + fma + half a max3); 36 with every term in its row.  "long solves": the 5 % of the
+            # workgroups with the most sweeps -- the waves that end a launch
+            long_wg = wsw >= np.percentile(wsw, 95)
+            for c, mask in enumerate(CERT_SETS):
+                rows = bin(mask).count("1")
+                f_all, f_l, f_w = out3[:, 35 + c].sum() / nsw, out3[long_wg, 35 + c].sum() / wsw[long_wg].sum(), out3[w, 35 + c] / max(wsw[w], 1)
+                cost = lambda f: 1.5 * rows + f * 2.5 * (24 - rows)
+                print("    set %#08x (%d rows): would be taken in %.2f %% of the wave sweeps (long solves %.2f %%, slowest workgroup %.2f %%); residual "
+                      "instructions per sweep %.1f (long solves %.1f, slowest %.1f) of 36" % (mask, rows, 100 * f_all, 100 * f_l, 100 * f_w, cost(f_all), cost(f_l), cost(f_w)))
 
 
 window(20, "first 20 steps after reset")
+g = torch.Generator(device="cuda"); g.manual_seed(1)
 for k in range(1500):
     env.step(acts[k % 8])
-window(100, "steady state (after 1500 steps)")
+    if STAGGER and k % 50 == 0 and k < 1300:      # bench.py Rollout.preroll
+        env.reset(torch.randperm(n, device="cuda", generator=g)[: max(1, n // 32)].to(torch.int32))
+window(100, "steady state (after 1500 steps%s)" % (", staggered resets" if STAGGER else ""))
