@@ -1031,11 +1031,13 @@ __device__ long long g_prof2[16 * 1024]; // per block: inside pgs_dv: [0] set-up
                                          // [4] substeps, [5] epilogue, [6] the 100 MHz counter over the kernel, [7] start of the last launch;
                                          // inside the sweeps: [8] link-box rows run, [9] joint-limit rows run, cycles of [10] the limit rows,
                                          // [11] link-box normals, [12] toe rows, [13] link-box friction rows, [14] sweeps of thread 0's env
-                                         // (what [8]-[13] cover)
+                                         // (what [8]-[13] cover); [15] cycles of the sweep BOUNDARIES of thread 0's env: from the end of toe
+                                         // row 23 to the start of row 1 of the env's next sweep (row 0, the exit tests and the loop between
+                                         // them; their number: g_prof3[47])
 __device__ long long g_prof3[48 * 1024]; // per block, per WAVE sweep (whatever thread 0's env does): [k] cycles and [17 + k] number of the sweeps that
                                          // began with k envs of the wave still running (k = 1..16); [34] sweeps that took the out-of-line residual
                                          // block (REX_RESIDUAL_ON_DEMAND); [35 + c] sweeps in which candidate certificate set c (REX_PROF_CERT_SETS)
-                                         // would have taken it
+                                         // would have taken it; [47] sweep boundaries counted in g_prof2[15]
 __device__ unsigned g_legmask[65536];   // per env: bits 0-7 the toe points in reach in the last substep, bits 8-15 their OR since the last read-out
 #define REX_STAMP(var) const long long var = clock64()
 /* -DREX_PROF_CERT_SETS=m0,m1,...,m11 on top (a build of its own: it adds work to every sweep; tools/prof_sections.py --cert holds the list):
@@ -1090,6 +1092,10 @@ __device__ unsigned g_legmask[65536];   // per env: bits 0-7 the toe points in r
    leg (0x55) in 79.1 % (tools/prof_sections.py --stagger --cert, profiles/residual_on_demand.md) */
 #ifndef REX_CERT_ROW_MASK
 #define REX_CERT_ROW_MASK 0x99u
+#endif
+/* the first joint-limit row of leg l + 1 read before leg l's rows are solved (pgs_dv, the kernels without link boxes) */
+#ifndef REX_LIMIT_ROWS_AHEAD
+#define REX_LIMIT_ROWS_AHEAD(EPW, ARM, BODY, MIXED) 1
 #endif
 __device__ __forceinline__ constexpr int crow_leg(int r) { return r < REX_NPOINT ? r / 2 : (r - REX_NPOINT) / 4; }
 __device__ __forceinline__ int crow_leg_rt(int r) { return r < REX_NPOINT ? r >> 1 : (r - REX_NPOINT) >> 2; }   // (a lane's own row index)
@@ -1180,6 +1186,7 @@ __device__ __forceinline__ void pgs_dv(const SM& sm, ARMP& armp, PgsX& x, int p,
   constexpr bool kPairedSweeps = REX_PAIRED_SWEEPS(EPW, ARMP::NM > 12, SM::kBody, LANECAP);
   constexpr bool kOnDemand = !INROW && REX_RESIDUAL_ON_DEMAND(EPW, ARMP::NM > 12, SM::kBody, LANECAP);   // the toe rows' residual (at the macro)
   static_assert(!kOnDemand || kPairedSweeps, "residual on demand: lo[r] - li[r] needs the two impulse sets");
+  constexpr bool kLimAhead = !INROW && !SM::kBody && REX_LIMIT_ROWS_AHEAD(EPW, ARMP::NM > 12, SM::kBody, LANECAP);   // (TRACE: the reads stay at their use)
   REX_STAMP(t_dv0);
   DvLane<NY, EPW> ln;   // toe rows: the lanes without a component read the zero in word 11
   DvLane<NY, EPW> lr;   // LDS-resident rows (joint limits, link boxes): zero word 9, (tgt, invd) in words 10-11
@@ -1270,6 +1277,9 @@ __device__ __forceinline__ void pgs_dv(const SM& sm, ARMP& armp, PgsX& x, int p,
   auto lim_load = [&](int r) __attribute__((always_inline)) { return slice_load<NY>(sm, lr, r * kRow, true); };   // joint-limit row r (rows REX_NCROW.. of the toe region)
   auto body_load = [&](int r, bool leg_part) __attribute__((always_inline)) { return slice_load<NY>(sm, lr, bodyoff + r * kRow, leg_part); };
   (void)body_load;
+#ifdef REX_PROF
+  long long prof_t23 = 0, prof_bnd = 0, prof_nbnd = 0;   // end of row 23 of the last toe block (0: none yet); boundary cycles and count
+#endif
   auto sweep = [&](const auto& li, auto& lo, int it) __attribute__((always_inline)) {
     ++nsweeps;
     // (`worst` lives outside the lane mask: a lane that has stopped keeps 0, and `running` is then one compare under the full EXEC --
@@ -1300,13 +1310,21 @@ __device__ __forceinline__ void pgs_dv(const SM& sm, ARMP& armp, PgsX& x, int p,
                                          lam + REX_NCROW + 3 * l, lam, worst, thr);
           }
         }
-      } else {
+      } else if (__builtin_expect(any_lim, 0)) {     // wave-uniform
+        // (the first row of leg l + 1 is read before leg l's rows are solved, whether that leg has a bound in reach or not -- the
+        //  link-box kernels' RunHead: otherwise every leg begins with a read nobody issued ahead)
+        RowSlice<NY> first[2];
+        if constexpr (kLimAhead) first[0] = lim_load(REX_NCROW);
 #pragma unroll
         for (int l = 0; l < REX_NLEG; ++l) {
-          if (__builtin_expect(!any_lim, 1)) break;  // wave-uniform
+          if constexpr (kLimAhead) {
+            if (l + 1 < REX_NLEG) first[(l + 1) & 1] = lim_load(REX_NCROW + 3 * l + 3);
+            prefetch_fence();
+          }
           if (!lim[l]) continue;                     // wave-uniform
           // (the three rows of a leg: the slice of row k + 1 is read from LDS while row k is solved)
-          RowSlice<NY> cur = lim_load(REX_NCROW + 3 * l);
+          RowSlice<NY> cur;
+          if constexpr (kLimAhead) cur = first[l & 1]; else cur = lim_load(REX_NCROW + 3 * l);
 #pragma unroll
           for (int k = 0; k < 3; ++k) {
             const int r = REX_NCROW + 3 * l + k;
@@ -1383,6 +1401,9 @@ __device__ __forceinline__ void pgs_dv(const SM& sm, ARMP& armp, PgsX& x, int p,
 #pragma unroll
         for (int r = 0; r < REX_NCROW; ++r) {
           const int L = crow_leg(r);
+#ifdef REX_PROF
+          if (r == 1 && prof_t23 != 0) { prof_bnd += clock64() - prof_t23; prof_nbnd += 1; }
+#endif
           const float sum = fmaf(cpl[r], dlp, S);
           float nl = fmaf(-Ki[r], sum, li[r]);
           if (r < REX_NPOINT) nl = fmaxf(nl, 0.0f);
@@ -1404,6 +1425,9 @@ __device__ __forceinline__ void pgs_dv(const SM& sm, ARMP& armp, PgsX& x, int p,
           for (int i = 0; i < NY; ++i) ys[i] = fmaf(Jy[r][i], dl, ys[i]);
           zs[L] = fmaf(Jz[r], dl, zs[L]);
         }
+#ifdef REX_PROF
+        prof_t23 = clock64();
+#endif
 #ifdef REX_PROF_CERT_SETS
         if constexpr (kOnDemand) {   // which certificate set: the sweeps in which each candidate would have taken the out-of-line block
           constexpr unsigned sets[12] = {REX_PROF_CERT_SETS};
@@ -1516,6 +1540,7 @@ __device__ __forceinline__ void pgs_dv(const SM& sm, ARMP& armp, PgsX& x, int p,
   if (threadIdx.x == 0 && blockIdx.x < 1024) {
     long long* p2 = g_prof2 + 16 * blockIdx.x;
     p2[0] += t_dv1 - t_dv0; p2[1] += t_dv2 - t_dv1; p2[2] += clock64() - t_dv2;
+    p2[15] += prof_bnd; g_prof3[48 * blockIdx.x + 47] += prof_nbnd;
   }
 #endif
 }

@@ -119,6 +119,10 @@ def window(steps, label):
         ca = out2[:, 10:14].sum(0) / nsa
         print("    all workgroups, per sweep: %.1f link-box rows + %.1f joint-limit rows; cycles: limit rows %.0f, link-box normals %.0f, toe rows %.0f, "
               "link-box friction %.0f" % (out2[:, 8].sum() / nsa, out2[:, 9].sum() / nsa, ca[0], ca[1], ca[2], ca[3]))
+    if out3[:, 47].sum() > 0:
+        # the sweep boundary of thread 0's env: end of toe row 23 -> start of row 1 of its next sweep (row 0, the exit tests, the loop)
+        print("  sweep boundary (row 23 -> row 1 of the next sweep): %.0f cycles, all workgroups (%.0f boundaries); %.0f in the slowest workgroup" %
+              (out2[:, 15].sum() / out3[:, 47].sum(), out3[:, 47].sum(), out2[w, 15] / max(out3[w, 47], 1)))
     if out3[:, 17:34].sum() > 0:
         # per WAVE sweep (whatever thread 0's env does), binned by the envs of the wave that still ran when the sweep began: does the
         # `if (running)` lane mask cost a partly stopped wave anything?
