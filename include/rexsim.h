@@ -679,6 +679,48 @@ typedef struct RexContactSolveOut {     /* any member may be NULL */
 } RexContactSolveOut;
 REX_API int rex_contact_solve(RexSim* sim, const int32_t* d_env_ids, int n, const RexContactSolveIn* in, const RexContactSolveOut* out, void* stream);
 
+/* Candidate rollouts (csrc/rex_rollout.h): for every row's env, K candidate command sequences simulated over T control steps of
+ * `repeat` substeps each, from the env's current state, in ONE read-only launch -- what a sampling planner (MPPI, CEM), a safety check
+ * before an action is applied or the scoring of a policy against its alternatives asks for.  The sim's state is never written; the
+ * step, settle and reset kernels are not involved.  Mark base only; toe rows and joint-limit rows only.  Rows, ids, stream and "no
+ * host sync" as rex_contact_solve; output row (k, c) is env d_env_ids[k] (or env k) under candidate c.
+ * One substep of a row, on its private copy W of the state's words 0..36 (position, quaternion, linear and angular velocity, joint
+ * angles and rates):
+ *   1. Torque.  `targets`: the motor model of the step's substep (rex_motor_torque / rex_motor_torque_params state it) on (cmd, q, qd,
+ *      qd) of W -- with the config's gains, or the env's actuator parameters of its current episode when a table or ranges are set
+ *      (rex_set_motor_params, rex_set_motor_randomization) -- multiplied by the env's enable bit in REX_S_MOTOR_EN as it stands at the
+ *      call.  `tau`: as given.  The command of control step t holds for its `repeat` substeps; the torque is drawn anew in each.
+ *   2. Contact solve.  v_next of rex_contact_solve with damping = 1 on W under that torque, with the env's mass scales, toe friction
+ *      and terrain field of its current episode; dt, iterations and residual_threshold as RexContactSolveIn.
+ *   3. Integrator.  The step's: semi-implicit Euler with the NEW velocities -- pos += dt lin, q += dt qd, the quaternion turned by
+ *      exp(dt w / 2) and normalised.
+ * Not advanced: the overheat counters and the motor mask (a motor that would overheat during the rollout keeps drawing torque),
+ * controller and gait words, step and episode counters (no reset, no done), sensor noise.
+ * Outputs (any member may be NULL, not all):  state, W after the last substep;  trajectory, W after every control step;
+ * foot_contact, 1 where either end of the leg's toe carries a positive normal impulse in the control step's last substep;  sweeps,
+ * the solver sweeps summed over the row's substeps.
+ * REX_EINVAL (message in rex_last_error) without a launch for: a null sim, in or out; both or neither of targets and tau; an `out`
+ * whose members are all NULL; n < 1; n > num_envs without ids; candidates < 1, steps < 1 or steps * repeat > 4096; an output of 2^31
+ * elements or more; iterations > 1000; a non-finite dt or threshold; a sim of mark arm, with on_rack, with body_contacts or with the
+ * latency model on (pd_latency or control_latency > 0: the observation ring is not restated). */
+typedef struct RexRolloutIn {
+  const float* targets;        /* [n][K][T][12] motor angle commands, rad (what d_motor_cmd / info['action'] hold), or NULL */
+  const float* tau;            /* [n][K][T][12] joint torques, N m, or NULL -- exactly one of the two */
+  int32_t candidates;          /* K >= 1 */
+  int32_t steps;               /* T >= 1 control steps */
+  int32_t repeat;              /* substeps per control step; <= 0: cfg.action_repeat */
+  float dt;                    /* <= 0: cfg.sim_time_step */
+  int32_t iterations;          /* <= 0: cfg.solver_iterations */
+  float residual_threshold;    /* < 0: cfg.solver_residual_threshold; 0: always `iterations` sweeps */
+} RexRolloutIn;
+typedef struct RexRolloutOut {   /* any member may be NULL, not all */
+  float* state;                /* [n][K][37]    words 0..36 of the state after the last substep */
+  float* trajectory;           /* [n][K][T][37] the same after every control step */
+  uint8_t* foot_contact;       /* [n][K][T][4]  a positive normal impulse at either end of the leg's toe in the control step's last substep */
+  int32_t* sweeps;             /* [n][K]        solver sweeps summed over the substeps */
+} RexRolloutOut;
+REX_API int rex_rollout(RexSim* sim, const int32_t* d_env_ids, int n, const RexRolloutIn* in, const RexRolloutOut* out, void* stream);
+
 /* The acceleration level (csrc/rex_contact_space.h): what a whole-body controller, a force-distribution QP or an analytic contact model
  * needs beside M, h and J_p -- each in one read-only launch, M(q) never written out, the state never written.  Mark base only.  Rows, ids
  * and launch as rex_dynamics: no host sync; v, the order of its 18 components, M, h, J_p, the masses (with the env's scales) and the toe

@@ -110,6 +110,18 @@ class RexContactSolveOut(ctypes.Structure):
                 ("sweeps", ctypes.c_void_p)]
 
 
+class RexRolloutIn(ctypes.Structure):
+    """Mirror of `struct RexRolloutIn` (include/rexsim.h): the commands (exactly one of targets and tau), the shape and the solver settings
+    of rex_rollout (repeat, dt, iterations <= 0, for the threshold < 0, take the config's)."""
+    _fields_ = [("targets", ctypes.c_void_p), ("tau", ctypes.c_void_p), ("candidates", ctypes.c_int32), ("steps", ctypes.c_int32),
+                ("repeat", ctypes.c_int32), ("dt", ctypes.c_float), ("iterations", ctypes.c_int32), ("residual_threshold", ctypes.c_float)]
+
+
+class RexRolloutOut(ctypes.Structure):
+    """Mirror of `struct RexRolloutOut` (include/rexsim.h): the device arrays rex_rollout fills (a null one is skipped)."""
+    _fields_ = [("state", ctypes.c_void_p), ("trajectory", ctypes.c_void_p), ("foot_contact", ctypes.c_void_p), ("sweeps", ctypes.c_void_p)]
+
+
 class RexContactSpaceOut(ctypes.Structure):
     """Mirror of `struct RexContactSpaceOut` (include/rexsim.h): the device arrays rex_contact_space fills (a null one is skipped)."""
     _fields_ = [("delassus", ctypes.c_void_p), ("toe_drift", ctypes.c_void_p), ("toe_acc_free", ctypes.c_void_p)]
@@ -229,6 +241,8 @@ _SIGS = {
     "rex_apply_impulse": ([ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(RexDynamicsLoad), ctypes.c_void_p, ctypes.c_void_p], ctypes.c_int),
     "rex_contact_solve": ([ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(RexContactSolveIn), ctypes.POINTER(RexContactSolveOut),
                            ctypes.c_void_p], ctypes.c_int),
+    "rex_rollout": ([ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(RexRolloutIn), ctypes.POINTER(RexRolloutOut), ctypes.c_void_p],
+                    ctypes.c_int),
     "rex_inverse_dynamics": ([ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(RexDynamicsLoad), ctypes.c_void_p,
                               ctypes.c_void_p], ctypes.c_int),
     "rex_contact_space": ([ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(RexContactSpaceOut),

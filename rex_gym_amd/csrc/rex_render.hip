@@ -141,3 +141,5 @@ hipError_t rex_launch_render(const RexSim* s, const rex::RenderCam& cam, const i
 #include "rex_contact_space.hip"
 // force distribution (rex_force_distribution): the same front end, then a fixed-length projected-gradient solve over the toe forces
 #include "rex_force_distribution.hip"
+// candidate rollouts (rex_rollout): the same front end and contact rows, substep after substep on a private copy of the state
+#include "rex_rollout.hip"

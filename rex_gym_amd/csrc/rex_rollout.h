@@ -1,0 +1,35 @@
+// rex_rollout.h -- candidate rollouts (rex_rollout.hip): for every row's env K candidate command sequences over T control steps of
+// `repeat` substeps each, from the env's current state, in one read-only launch on the lane mapping, the front end (rex_dynamics_leg.h)
+// and the contact rows (rex_contact_rows.h) of rex_contact_solve.  The step, settle and reset kernels are not involved and the sim's
+// state is never written.  Mark base only; toe rows and joint-limit rows only (no link-box rows, no on_rack anchor, no latency ring).
+//
+// The substep and what is not advanced are stated once, at rex_rollout in include/rexsim.h.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include "../../include/rexsim.h"
+
+struct RexSim;
+
+namespace rex {
+
+constexpr int kRolloutMaxSubsteps = 4096;     // steps x repeat: the substep loop is bounded on the host
+constexpr int kRolloutWords = 37;             // words 0..36 of the state: position, quaternion, velocities, joint angles and rates
+
+// What one launch does; every member is the same for every thread.  The host has resolved the defaults of RexRolloutIn.
+struct RexRolloutArgs {
+  const float* targets;      // [n][K][T][12] motor angle commands, or null
+  const float* tau;          // [n][K][T][12] joint torques, or null -- exactly one of the two
+  int K, T, repeat;          // >= 1; T * repeat <= kRolloutMaxSubsteps
+  float dt;                  // > 0
+  int iterations;            // 1 .. kContactMaxIterations
+  float threshold;           // >= 0; 0: every substep runs `iterations` sweeps
+  int motor;                 // 1: the env's actuator parameters are in effect (a table or ranges are set)
+  RexRolloutOut out;         // null members are skipped
+};
+
+}  // namespace rex
+
+// One rex_rollout_kernel over n * K rows (row r = env d_ids[r / K], or env r / K with d_ids null; candidate r % K).  Arguments are
+// checked by the caller (rexsim.hip).
+hipError_t rex_launch_rollout(const RexSim* s, const int32_t* d_ids, int n, const rex::RexRolloutArgs& a, hipStream_t st);

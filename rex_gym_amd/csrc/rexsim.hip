@@ -13,6 +13,7 @@
 #include "rex_dynamics.h"
 #include "rex_dynamics_solve.h"
 #include "rex_contact_solve.h"
+#include "rex_rollout.h"
 #include "rex_contact_space.h"
 #include "rex_force_distribution.h"
 #include "rex_visual_gen.h"
@@ -1240,6 +1241,44 @@ int rex_contact_solve(RexSim* s, const int32_t* d_env_ids, int n, const RexConta
   if (!(a.dt > 0.0f) || !std::isfinite(a.dt) || !(a.threshold >= 0.0f) || !std::isfinite(a.threshold))
     return failf(REX_EINVAL, "%s: dt %g, residual_threshold %g: a finite dt > 0 and a finite threshold", who, (double)in->dt, (double)in->residual_threshold);
   READOUT_LAUNCH(rex_launch_contact_solve, a);
+}
+
+static_assert(sizeof(RexRolloutIn) == 40 && sizeof(RexRolloutOut) == 32, "RexRolloutIn: two pointers, six 4-byte words; RexRolloutOut: 4 pointers (rex_gym_amd/_lib.py mirrors them)");
+
+// (what the arguments alone decide comes first, in front of everything the sim decides: those refusals need no device)
+int rex_rollout(RexSim* s, const int32_t* d_env_ids, int n, const RexRolloutIn* in, const RexRolloutOut* out, void* stream) {
+  const char* who = "rex_rollout";
+  if (!in || !out) return failf(REX_EINVAL, "%s: null pointer", who);
+  if ((in->targets != nullptr) == (in->tau != nullptr)) return failf(REX_EINVAL, "%s: exactly one of targets and tau", who);
+  if (!out->state && !out->trajectory && !out->foot_contact && !out->sweeps) return failf(REX_EINVAL, "%s: every output pointer is null", who);
+  const int K = in->candidates, T = in->steps;
+  if (K < 1) return failf(REX_EINVAL, "%s: candidates %d: at least one candidate per env", who, K);
+  if (T < 1) return failf(REX_EINVAL, "%s: steps %d: at least one control step", who, T);
+  if (T > rex::kRolloutMaxSubsteps || (in->repeat > 0 && (long long)T * in->repeat > rex::kRolloutMaxSubsteps))
+    return failf(REX_EINVAL, "%s: steps %d x repeat %d: at most %d substeps", who, T, in->repeat, rex::kRolloutMaxSubsteps);
+  if (in->iterations > rex::kContactMaxIterations) return failf(REX_EINVAL, "%s: iterations %d: 1 .. %d", who, in->iterations, rex::kContactMaxIterations);
+  if (!std::isfinite(in->dt) || !std::isfinite(in->residual_threshold))
+    return failf(REX_EINVAL, "%s: dt %g, residual_threshold %g: a finite dt > 0 and a finite threshold", who, (double)in->dt, (double)in->residual_threshold);
+  const int rows_err = solve_rows(who, s, d_env_ids, n);               // a null sim, n < 1, n > num_envs without ids, mark arm
+  if (rows_err != REX_OK) return rows_err;
+  // (K <= 2^31 - 1 and T <= 4096: the products stay inside 64 bits)
+  if ((long long)n * K >= (1ll << 31) || (long long)n * K * T * rex::kRolloutWords >= (1ll << 31))
+    return failf(REX_EINVAL, "%s: n %d, candidates %d, steps %d: n * candidates * steps * 37 must stay below 2^31", who, n, K, T);
+  if (s->cfg.on_rack) return failf(REX_EINVAL, "%s: an on_rack sim holds its base with an anchor the rollout leaves out", who);
+  if (s->cfg.body_contacts) return failf(REX_EINVAL, "%s: a sim with body_contacts solves link-box rows the rollout leaves out", who);
+  if (has_latency(s->cfg))
+    return failf(REX_EINVAL, "%s: a sim with the latency model on (pd_latency or control_latency > 0) draws its torques from an observation ring the rollout does not restate", who);
+  const int repeat = in->repeat > 0 ? in->repeat : s->cfg.action_repeat;
+  if (repeat < 1 || (long long)T * repeat > rex::kRolloutMaxSubsteps)
+    return failf(REX_EINVAL, "%s: steps %d x repeat %d: at most %d substeps", who, T, repeat, rex::kRolloutMaxSubsteps);
+  rex::RexRolloutArgs a{in->targets, in->tau, K, T, repeat, in->dt > 0.0f ? in->dt : s->cfg.sim_time_step,
+                        in->iterations > 0 ? in->iterations : s->cfg.solver_iterations,
+                        in->residual_threshold < 0.0f ? s->cfg.solver_residual_threshold : in->residual_threshold, rex::motor_params_on(s->mot) ? 1 : 0, *out};
+  if (a.iterations < 1 || a.iterations > rex::kContactMaxIterations)
+    return failf(REX_EINVAL, "%s: iterations %d: 1 .. %d", who, a.iterations, rex::kContactMaxIterations);
+  if (!(a.dt > 0.0f) || !std::isfinite(a.dt) || !(a.threshold >= 0.0f) || !std::isfinite(a.threshold))
+    return failf(REX_EINVAL, "%s: dt %g, residual_threshold %g: a finite dt > 0 and a finite threshold", who, (double)a.dt, (double)a.threshold);
+  READOUT_LAUNCH(rex_launch_rollout, a);
 }
 
 static_assert(sizeof(RexContactSpaceOut) == 24, "RexContactSpaceOut: 3 pointers, no padding (rex_gym_amd/_lib.py mirrors it)");
