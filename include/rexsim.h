@@ -721,6 +721,37 @@ typedef struct RexRolloutOut {   /* any member may be NULL, not all */
 } RexRolloutOut;
 REX_API int rex_rollout(RexSim* sim, const int32_t* d_env_ids, int n, const RexRolloutIn* in, const RexRolloutOut* out, void* stream);
 
+/* Candidate rollouts from given states, under base pushes and per-candidate bodies: rex_rollout with up to three per-row inputs in place
+ * of what the row would take from its env -- what beam or tree search over `state`, horizons past 4096 substeps (chain the calls),
+ * rollouts from an estimated or perturbed state (finite-difference linearisation), "does this action survive a shove" and the scoring
+ * of candidates under several mass and friction draws ask for.  The same launch shape, substep, outputs and "no host sync" as
+ * rex_rollout; row (k, c) is env d_env_ids[k] (or env k) under candidate c.  Every member of `from` is a float32 device array or NULL;
+ * with all three NULL the call computes what rex_rollout computes.
+ *   init_state   W of row (k, c) starts as these 37 words -- position, quaternion x y z w, linear and angular velocity, joint angles and
+ *                rates, the layout of `state` and `trajectory` -- instead of the env's words 0..36.  Taken as given: the quaternion is not
+ *                normalised, nothing is checked, nothing is read back on the host.  Feeding a call's `state` output to the next call
+ *                continues the rollout bit for bit: W is emitted as it is held.
+ *   base_wrench  a world force at the base origin, N, then a world moment, N m -- the convention of rex_forward_dynamics' base wrench --
+ *                for control step t of row (k, c), held over its `repeat` substeps.  It enters step 1 of the substep,
+ *                v* = v + dt M^-1 (S^T tau + w - h - d); the rows and the sweeps follow from v* as before.  A wrench of zeros changes no bit.
+ *   body         base mass scale, leg mass scale and toe friction of row (k, c), in place of the env's (rex_set_body_params'
+ *                triple: the scales touch the masses only, as everywhere else; mu is the friction of the row's toe rows).
+ * Everything else a row reads stays its env's at the call: the terrain field of the env's episode, its actuator parameters, its motor
+ * enable bits, and whichever of the three is NULL.
+ * The states are the caller's, so the kernel was read for arbitrary float input: the one address formed from W, the heightfield lookup
+ * under the toe points, clamps its grid coordinates (a NaN lands on cell 0), every table is addressed by launch constants and every
+ * loop is bounded by steps, repeat and iterations.  A bad row -- non-finite, huge, a zero quaternion -- yields garbage in that row only.
+ * REX_EINVAL (message in rex_last_error) without a launch for everything rex_rollout refuses, and for a NULL `from`.  The three inputs
+ * count towards the 2^31-element limit (each is smaller than `trajectory`'s n * K * T * 37, which is held below 2^31 whether it is
+ * asked for or not). */
+typedef struct RexRolloutFrom {      /* any member may be NULL; all NULL: rex_rollout */
+  const float* init_state;           /* [n][K][37] words 0..36 each row starts from, instead of the env's state */
+  const float* base_wrench;          /* [n][K][T][6] world force at the base origin and moment, N / N m, held over the control step's substeps */
+  const float* body;                 /* [n][K][3] base mass scale, leg mass scale, toe friction of the row, instead of the env's */
+} RexRolloutFrom;
+REX_API int rex_rollout_from(RexSim* sim, const int32_t* d_env_ids, int n, const RexRolloutIn* in, const RexRolloutFrom* from,
+                             const RexRolloutOut* out, void* stream);
+
 /* The acceleration level (csrc/rex_contact_space.h): what a whole-body controller, a force-distribution QP or an analytic contact model
  * needs beside M, h and J_p -- each in one read-only launch, M(q) never written out, the state never written.  Mark base only.  Rows, ids
  * and launch as rex_dynamics: no host sync; v, the order of its 18 components, M, h, J_p, the masses (with the env's scales) and the toe

@@ -122,6 +122,12 @@ class RexRolloutOut(ctypes.Structure):
     _fields_ = [("state", ctypes.c_void_p), ("trajectory", ctypes.c_void_p), ("foot_contact", ctypes.c_void_p), ("sweeps", ctypes.c_void_p)]
 
 
+class RexRolloutFrom(ctypes.Structure):
+    """Mirror of `struct RexRolloutFrom` (include/rexsim.h): what rex_rollout_from takes per row in place of the env's own -- the state the
+    row starts from, the base wrench of every control step, the body parameters (a null one: the env's, or no wrench)."""
+    _fields_ = [("init_state", ctypes.c_void_p), ("base_wrench", ctypes.c_void_p), ("body", ctypes.c_void_p)]
+
+
 class RexContactSpaceOut(ctypes.Structure):
     """Mirror of `struct RexContactSpaceOut` (include/rexsim.h): the device arrays rex_contact_space fills (a null one is skipped)."""
     _fields_ = [("delassus", ctypes.c_void_p), ("toe_drift", ctypes.c_void_p), ("toe_acc_free", ctypes.c_void_p)]
@@ -243,6 +249,8 @@ _SIGS = {
                            ctypes.c_void_p], ctypes.c_int),
     "rex_rollout": ([ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(RexRolloutIn), ctypes.POINTER(RexRolloutOut), ctypes.c_void_p],
                     ctypes.c_int),
+    "rex_rollout_from": ([ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(RexRolloutIn), ctypes.POINTER(RexRolloutFrom),
+                          ctypes.POINTER(RexRolloutOut), ctypes.c_void_p], ctypes.c_int),
     "rex_inverse_dynamics": ([ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(RexDynamicsLoad), ctypes.c_void_p,
                               ctypes.c_void_p], ctypes.c_int),
     "rex_contact_space": ([ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(RexContactSpaceOut),

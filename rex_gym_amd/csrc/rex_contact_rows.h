@@ -32,9 +32,14 @@ struct ConRows {
 };
 
 // ---- 1. the free velocity ----
-// bf: the leg's joint torques on entry (the bias and the damping are taken off here)
+// bf: the leg's joint torques on entry (the bias and the damping are taken off here).  WRENCH: wrench [6] is a world force at the base
+// origin and a world moment (rex_forward_dynamics' base_wrench), the same on every lane of the quad; else it is not read.  Ft, Nt are
+// the bias wrench about the base origin, so the wrench is taken off them once per row, behind the quad sum; x - (+0) is x: a zero
+// wrench changes no bit.  (A template argument, so that the callers without a wrench compile to the code they had:
+// profiles/rollout_from.md)
+template <bool WRENCH = false>
 __device__ __forceinline__ void con_free_velocity(const DynFront& F, const DynFactor& Q, float (&bf)[3], int damping, float dt, float (&vs0)[6],
-                                                  float (&vsf)[3]) {
+                                                  float (&vsf)[3], const float* wrench = nullptr) {
   const DynLeg& L = F.L;
   f3 Fs[3], Ns[3];
   leg_bias(L, F.w0, Fs, Ns);
@@ -59,7 +64,11 @@ __device__ __forceinline__ void con_free_velocity(const DynFront& F, const DynFa
     F0 = F0 + (F.base * F.m0 * dl0) * F.v0;
     N0 = N0 + (F.base * da0) * mul(F.I0, F.w0);
   }
-  const f3 Ft = quad_sum(Fs[0] + F0), Nt = quad_sum(Ns[0] + N0);
+  f3 Ft = quad_sum(Fs[0] + F0), Nt = quad_sum(Ns[0] + N0);
+  if constexpr (WRENCH) {
+    Ft = Ft - mk(wrench[0], wrench[1], wrench[2]);
+    Nt = Nt - mk(wrench[3], wrench[4], wrench[5]);
+  }
 #pragma unroll
   for (int i = 0; i < 3; ++i) bf[i] -= dot(L.a[i], Ns[i] - cross(L.p[i], Fs[i]));
   const float b0[6] = {-Ft.x, -Ft.y, -Ft.z, -Nt.x, -Nt.y, -Nt.z};

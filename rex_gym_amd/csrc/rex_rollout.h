@@ -33,3 +33,9 @@ struct RexRolloutArgs {
 // One rex_rollout_kernel over n * K rows (row r = env d_ids[r / K], or env r / K with d_ids null; candidate r % K).  Arguments are
 // checked by the caller (rexsim.hip).
 hipError_t rex_launch_rollout(const RexSim* s, const int32_t* d_ids, int n, const rex::RexRolloutArgs& a, hipStream_t st);
+
+// The same over rows that take the state they start from, a base wrench per control step and their body parameters from the caller
+// (rex_rollout_from in include/rexsim.h): the kernel's other instantiation, row r reads from.init_state + r * 37, from.base_wrench +
+// (r * T + t) * 6 and from.body + r * 3; a null member leaves the env's own in place (no wrench).
+hipError_t rex_launch_rollout_from(const RexSim* s, const int32_t* d_ids, int n, const rex::RexRolloutArgs& a, const RexRolloutFrom& from,
+                                   hipStream_t st);

@@ -17,7 +17,25 @@
 // is only read (state, commands) and written (outputs); the sim's state is not written.  Not advanced: overheat counters and the motor
 // mask, controller and gait words, step and episode counters, sensor noise.  Lanes of rows past the end repeat the last row, take every
 // barrier, quad sum and ballot, and store nothing to global memory.
+//
+// The kernel is a template over its argument.  With RexRolloutLaunch it is rex_rollout's, as above.  With RexRolloutFromLaunch it is
+// rex_rollout_from's (rex_rollout.h), the same source with three reads more, each behind a launch-uniform null test:
+//   load    W from init_state + row * 37 instead of the state;
+//   body    after env_ground, the two mass scales and mu of the row's Ground from body + row * 3;
+//   wrench  base_wrench + (row * T + t) * 6, read beside the command once per control step and handed to con_free_velocity, which takes
+//           it off the bias wrench about the base origin (zeros when the pointer is null: x - (+0) is x, the same bits).
+// W is then the caller's, so what a row computes from W was read for arbitrary float input, non-finite and huge values included:
+//   - the only address formed from W is ground_query's (rex_device.h), under the toe points: the grid coordinate goes through
+//     fminf(fmaxf(x, 0), max) before the conversion to int -- a NaN comes out as 0, an infinity as a bound -- so the four heights read
+//     lie inside the env's field; the field itself (Ground::off, mid) comes from the env's episode word, never from W;
+//   - the FK tables and W in LDS are addressed by the lane's row and leg, constants of the launch; the rows of ConRows by unrolled
+//     constants; the motor model's table is a minimum of lines; sincos_fast and sincosf reduce in registers, their quadrant is used in
+//     selects only;
+//   - the loops run T, repeat and at most `iterations` times, all launch-uniform; con_sweeps leaves early on a ballot but never later.
+// A bad row yields garbage in that row only: rows share nothing but the barriers and the ballot of the sweep loop's early exit, which a
+// row that never converges can only hold to the `iterations` every row is allowed anyway.
 // (Built as part of rex_render.hip's object, like rex_contact_solve.hip: rex_gym_amd/build.py INCLUDED_IN.)
+#include <type_traits>
 #include "rex_render_common.h"
 #include "rex_rollout.h"
 #include "rex_contact_rows.h"
@@ -33,12 +51,15 @@ static_assert(kRolloutFkFloats * (int)sizeof(float) == kDynFkBytes && kRolloutBy
 static_assert(REX_S_POS == 0 && REX_S_QUAT == 3 && REX_S_LINVEL == 7 && REX_S_ANGVEL == 10 && Lay<REX_NUM_MOTORS>::Q == 13 &&
               Lay<REX_NUM_MOTORS>::QD + REX_NUM_MOTORS == kRolloutWords, "W holds the words 0..36 in the state's order");
 
-// the kernel's argument: the launch's settings and the sim's actuator knobs
+// the kernel's argument: the launch's settings and the sim's actuator knobs; for rex_rollout_from the per-row inputs behind them
 struct RexRolloutLaunch { RexRolloutArgs a; MotDev mot; };
+struct RexRolloutFromLaunch : RexRolloutLaunch { RexRolloutFrom from; };
 
+template <class Launch>
 __global__ void __launch_bounds__(kDynThreads) rex_rollout_kernel(DevCfg c, const float* __restrict__ state, const int32_t* __restrict__ ids,
-                                                                  int rows_total, RexRolloutLaunch la) {
+                                                                  int rows_total, Launch la) {
   constexpr int NM = REX_NUM_MOTORS, NE = kDynEnvs;
+  constexpr bool FROM = std::is_same<Launch, RexRolloutFromLaunch>::value;
   extern __shared__ __attribute__((aligned(16))) float s_roll[];
   const RexRolloutArgs& a = la.a;
   const int el0 = threadIdx.x >> 2, leg0 = threadIdx.x & 3, el = el0, leg = leg0;
@@ -49,9 +70,25 @@ __global__ void __launch_bounds__(kDynThreads) rex_rollout_kernel(DevCfg c, cons
   float* W = s_roll + kRolloutFkFloats;                              // [kRolloutWords][NE]: word w of this row at W[w * NE + el]
 
   // ---- the row's copy of the state, and what stays as it is at the call ----
-  for (int w = leg; w < kRolloutWords; w += 4) W[w * NE + el] = ldw(state, c.n, w, env);
+  if constexpr (FROM) {
+    if (la.from.init_state) {                                        // (every pointer of `from` is the same in every thread)
+      const float* src = la.from.init_state + (size_t)row * kRolloutWords;
+      for (int w = leg; w < kRolloutWords; w += 4) W[w * NE + el] = src[w];
+    } else {
+      for (int w = leg; w < kRolloutWords; w += 4) W[w * NE + el] = ldw(state, c.n, w, env);
+    }
+  } else {
+    for (int w = leg; w < kRolloutWords; w += 4) W[w * NE + el] = ldw(state, c.n, w, env);
+  }
   const int gidx = c.env_index_base + env, episode = (int)ldi(state, c.n, Lay<NM>::EPISODE, env);
-  const Ground g = env_ground(c, env, gidx, episode);
+  Ground ground = env_ground(c, env, gidx, episode);
+  if constexpr (FROM) {
+    if (la.from.body) {
+      const float* b = la.from.body + (size_t)row * 3;
+      ground.base_mass_scale = b[0]; ground.leg_mass_scale = b[1]; ground.mu = b[2];
+    }
+  }
+  const Ground g = ground;
   const uint32_t motor_en = ldi(state, c.n, Lay<NM>::MOTOR_EN, env);
   MotorScalars mp{kMotorVoltage, 0.0f, c.kp, c.kd};
   float strength[3] = {1.0f, 1.0f, 1.0f};
@@ -71,6 +108,14 @@ __global__ void __launch_bounds__(kDynThreads) rex_rollout_kernel(DevCfg c, cons
     {
       const float* p = commands + ((size_t)row * a.T + t) * 12 + 3 * leg;
       cmd[0] = p[0]; cmd[1] = p[1]; cmd[2] = p[2];
+    }
+    float wrench[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};                // (FROM only) the control step's base wrench, on every lane of the row
+    if constexpr (FROM) {
+      if (la.from.base_wrench) {
+        const float* p = la.from.base_wrench + ((size_t)row * a.T + t) * 6;
+#pragma unroll
+        for (int i = 0; i < 6; ++i) wrench[i] = p[i];
+      }
     }
     bool touch = false;
     for (int r = 0; r < a.repeat; ++r) {
@@ -108,7 +153,8 @@ __global__ void __launch_bounds__(kDynThreads) rex_rollout_kernel(DevCfg c, cons
 
       // ---- 2. v_next of rex_contact_solve with damping = 1 ----
       float vs0[6], vsf[3];
-      con_free_velocity(F, Q, bf, 1, dt, vs0, vsf);
+      if constexpr (FROM) con_free_velocity<true>(F, Q, bf, 1, dt, vs0, vsf, wrench);
+      else con_free_velocity(F, Q, bf, 1, dt, vs0, vsf);
       ConRows P;
       con_build_rows(W, NE, el, leg, field, F, Q, dt, vs0, vsf, P);
       count += con_sweeps(P, g.mu, leg, a.iterations, a.threshold);
@@ -168,5 +214,11 @@ __global__ void __launch_bounds__(kDynThreads) rex_rollout_kernel(DevCfg c, cons
 
 hipError_t rex_launch_rollout(const RexSim* s, const int32_t* d_ids, int n, const rex::RexRolloutArgs& a, hipStream_t st) {
   const rex::RexRolloutLaunch la{a, s->mot};
-  return rex::dyn_launch(rex::rex_rollout_kernel, rex::kRolloutBytes, s, d_ids, n * a.K, la, st);
+  return rex::dyn_launch(rex::rex_rollout_kernel<rex::RexRolloutLaunch>, rex::kRolloutBytes, s, d_ids, n * a.K, la, st);
+}
+
+hipError_t rex_launch_rollout_from(const RexSim* s, const int32_t* d_ids, int n, const rex::RexRolloutArgs& a, const RexRolloutFrom& from,
+                                   hipStream_t st) {
+  const rex::RexRolloutFromLaunch la{{a, s->mot}, from};
+  return rex::dyn_launch(rex::rex_rollout_kernel<rex::RexRolloutFromLaunch>, rex::kRolloutBytes, s, d_ids, n * a.K, la, st);
 }

@@ -1244,11 +1244,12 @@ int rex_contact_solve(RexSim* s, const int32_t* d_env_ids, int n, const RexConta
 }
 
 static_assert(sizeof(RexRolloutIn) == 40 && sizeof(RexRolloutOut) == 32, "RexRolloutIn: two pointers, six 4-byte words; RexRolloutOut: 4 pointers (rex_gym_amd/_lib.py mirrors them)");
+static_assert(sizeof(RexRolloutFrom) == 24, "RexRolloutFrom: 3 pointers, no padding (rex_gym_amd/_lib.py mirrors it)");
 
+// what rex_rollout and rex_rollout_from refuse alike, and the launch's settings with the config's defaults resolved -> a
 // (what the arguments alone decide comes first, in front of everything the sim decides: those refusals need no device)
-int rex_rollout(RexSim* s, const int32_t* d_env_ids, int n, const RexRolloutIn* in, const RexRolloutOut* out, void* stream) {
-  const char* who = "rex_rollout";
-  if (!in || !out) return failf(REX_EINVAL, "%s: null pointer", who);
+static int rollout_args(const char* who, RexSim* s, const int32_t* d_env_ids, int n, const RexRolloutIn* in, const RexRolloutOut* out,
+                        rex::RexRolloutArgs& a) {
   if ((in->targets != nullptr) == (in->tau != nullptr)) return failf(REX_EINVAL, "%s: exactly one of targets and tau", who);
   if (!out->state && !out->trajectory && !out->foot_contact && !out->sweeps) return failf(REX_EINVAL, "%s: every output pointer is null", who);
   const int K = in->candidates, T = in->steps;
@@ -1271,14 +1272,36 @@ int rex_rollout(RexSim* s, const int32_t* d_env_ids, int n, const RexRolloutIn* 
   const int repeat = in->repeat > 0 ? in->repeat : s->cfg.action_repeat;
   if (repeat < 1 || (long long)T * repeat > rex::kRolloutMaxSubsteps)
     return failf(REX_EINVAL, "%s: steps %d x repeat %d: at most %d substeps", who, T, repeat, rex::kRolloutMaxSubsteps);
-  rex::RexRolloutArgs a{in->targets, in->tau, K, T, repeat, in->dt > 0.0f ? in->dt : s->cfg.sim_time_step,
-                        in->iterations > 0 ? in->iterations : s->cfg.solver_iterations,
-                        in->residual_threshold < 0.0f ? s->cfg.solver_residual_threshold : in->residual_threshold, rex::motor_params_on(s->mot) ? 1 : 0, *out};
+  a = rex::RexRolloutArgs{in->targets, in->tau, K, T, repeat, in->dt > 0.0f ? in->dt : s->cfg.sim_time_step,
+                          in->iterations > 0 ? in->iterations : s->cfg.solver_iterations,
+                          in->residual_threshold < 0.0f ? s->cfg.solver_residual_threshold : in->residual_threshold, rex::motor_params_on(s->mot) ? 1 : 0, *out};
   if (a.iterations < 1 || a.iterations > rex::kContactMaxIterations)
     return failf(REX_EINVAL, "%s: iterations %d: 1 .. %d", who, a.iterations, rex::kContactMaxIterations);
   if (!(a.dt > 0.0f) || !std::isfinite(a.dt) || !(a.threshold >= 0.0f) || !std::isfinite(a.threshold))
     return failf(REX_EINVAL, "%s: dt %g, residual_threshold %g: a finite dt > 0 and a finite threshold", who, (double)a.dt, (double)a.threshold);
+  return REX_OK;
+}
+
+int rex_rollout(RexSim* s, const int32_t* d_env_ids, int n, const RexRolloutIn* in, const RexRolloutOut* out, void* stream) {
+  const char* who = "rex_rollout";
+  if (!in || !out) return failf(REX_EINVAL, "%s: null pointer", who);
+  rex::RexRolloutArgs a;
+  const int args_err = rollout_args(who, s, d_env_ids, n, in, out, a);
+  if (args_err != REX_OK) return args_err;
   READOUT_LAUNCH(rex_launch_rollout, a);
+}
+
+// (the three inputs hold n * K * 37, n * K * T * 6 and n * K * 3 elements: each below the n * K * T * 37 that rollout_args holds under 2^31)
+int rex_rollout_from(RexSim* s, const int32_t* d_env_ids, int n, const RexRolloutIn* in, const RexRolloutFrom* from, const RexRolloutOut* out,
+                     void* stream) {
+  const char* who = "rex_rollout_from";
+  if (!in || !from || !out) return failf(REX_EINVAL, "%s: null pointer", who);
+  rex::RexRolloutArgs a;
+  const int args_err = rollout_args(who, s, d_env_ids, n, in, out, a);
+  if (args_err != REX_OK) return args_err;
+  HIPCHK(hipSetDevice(s->device));
+  HIPCHK(rex_launch_rollout_from(s, d_env_ids, n, a, *from, (hipStream_t)stream));
+  return REX_OK;
 }
 
 static_assert(sizeof(RexContactSpaceOut) == 24, "RexContactSpaceOut: 3 pointers, no padding (rex_gym_amd/_lib.py mirrors it)");

@@ -698,7 +698,8 @@ class RexBatchEnv:
         return contact.solve(self, tau, env_ids, fields, out, dt, iterations, residual_threshold, damping)
 
     # ---- candidate rollouts (rex_gym_amd/rollout.py) ----
-    def rollout(self, targets=None, tau=None, repeat=None, env_ids=None, fields=None, out=None, dt=None, iterations=None, residual_threshold=None):
+    def rollout(self, targets=None, tau=None, repeat=None, env_ids=None, fields=None, out=None, dt=None, iterations=None, residual_threshold=None,
+                init_state=None, base_wrench=None, body=None):
         """Where every env is after T control steps under each of K candidate command sequences (rex_rollout): simulated from the
         current state on a private copy, in ONE read-only launch on the env's device and stream, no host sync; the state is never
         written.  Commands: exactly one of targets -- motor angle commands, rad, what info['action'] holds -- and tau -- joint
@@ -716,9 +717,18 @@ class RexBatchEnv:
         NOT advanced: the overheat counters and the motor mask, controller and gait words, step and episode counters (no reset, no
         done), sensor noise.  fields, out: as in kinematics().  Mark 'arm' raises NotImplementedError; on_rack, body_contacts and
         latency-model envs raise ValueError (the anchor, the link-box rows and the observation ring are not restated).  Every argument
-        error is raised before any launch."""
+        error is raised before any launch.
+        Per-row inputs in place of the env's own (rex_rollout_from; float32 device tensors, contiguous, each may be None):
+          init_state [k, K, 37] or [k, 37] (every candidate alike): the words 0..36 each row starts from -- a previous call's `state`
+              continues that rollout bit for bit (beam search, horizons past 4096 substeps); an estimated or perturbed state.  Taken as
+              given: not normalised, not checked; a bad row yields garbage in that row only
+          base_wrench [k, K, T, 6]: a world force at the base origin, N, and a world moment, N m (forward_dynamics()' convention), held
+              over the control step's substeps: v* = v + dt M^-1 (S^T tau + w - bias - damping)
+          body [k, K, 3]: base mass scale, leg mass scale, toe friction of the row (set_body_params' triple)
+        The terrain field, the actuator parameters and the motor enable bits stay the env's.  With all three None the call is
+        rex_rollout as before."""
         from .. import rollout
-        return rollout.run(self, targets, tau, repeat, env_ids, fields, out, dt, iterations, residual_threshold)
+        return rollout.run(self, targets, tau, repeat, env_ids, fields, out, dt, iterations, residual_threshold, init_state, base_wrench, body)
 
     # ---- the acceleration level (rex_gym_amd/contact_space.py) ----
     def inverse_dynamics(self, vdot=None, tau=None, toe_forces=None, base_wrench=None, env_ids=None, out=None):

@@ -17,7 +17,17 @@ integrator: pos += dt lin, q += dt qd, the quaternion turned by exp(dt w / 2) an
 `repeat` substeps; the torque is drawn anew in each.
 
 Not advanced: the overheat counters and the motor mask, controller and gait words, step and episode counters (no reset, no done), sensor
-noise.  The env's state is never written."""
+noise.  The env's state is never written.
+
+From given states, under base pushes, in other bodies (rex_rollout_from; each input is per row, any may be left out):
+
+    nxt = env.rollout(targets=targets[:, :, 2:], init_state=ro.state)          # continue where `ro` stopped: bit for bit the unsplit call
+    env.rollout(targets=targets, base_wrench=w)                                # w [k, K, T, 6]: world force at the base origin, N, and moment, N m
+    env.rollout(targets=targets, body=b)                                       # b [k, K, 3]: base mass scale, leg mass scale, toe friction
+
+init_state [k, K, 37] (or [k, 37], the same for every candidate) is taken as given -- not normalised, not checked: a bad row yields garbage
+in that row only.  The wrench of control step t holds over its substeps and enters the free velocity, v* = v + dt M^-1 (S^T tau + w - h - d).
+Everything else a row reads -- terrain field, actuator parameters, motor enable bits -- stays its env's at the call."""
 import ctypes
 
 from . import _lib, contact, readout
@@ -114,6 +124,25 @@ def check_commands(env, targets, tau, k):
     return t, K, T
 
 
+def check_from(env, init_state, base_wrench, body, k, K, T):
+    """the per-row inputs of rex_rollout_from, each None or float32 on the env's device, contiguous: init_state [k, K, 37] (or [k, 37], the
+    same for every candidate), base_wrench [k, K, T, 6], body [k, K, 3] -> the three tensors as the launch reads them (None stays None)"""
+    torch, who = env._torch, "rollout"
+    shapes = {"init_state": (k, K, WORDS), "base_wrench": (k, K, T, 6), "body": (k, K, 3)}
+    given = {"init_state": init_state, "base_wrench": base_wrench, "body": body}
+    for name, t in given.items():
+        if t is None:
+            continue
+        if not (isinstance(t, torch.Tensor) and t.dtype == torch.float32 and t.device == env.device):
+            raise ValueError(f"{who}: {name} must be a float32 tensor on {env.device}")
+        either = " or (%d, %d)" % (k, WORDS) if name == "init_state" else ""
+        if not ((tuple(t.shape) == shapes[name] or (name == "init_state" and tuple(t.shape) == (k, WORDS))) and t.is_contiguous()):
+            raise ValueError(f"{who}: {name} must be contiguous with shape {shapes[name]}{either}, got {tuple(t.shape)}")
+    if init_state is not None and init_state.dim() == 2:
+        given["init_state"] = init_state[:, None, :].expand(k, K, WORDS).contiguous()
+    return given["init_state"], given["base_wrench"], given["body"]
+
+
 def check_result(out, names, k, K, T, env):
     """a result handed back through out=: its class and fields, then each tensor's shape, dtype, device and identity"""
     torch, who = env._torch, "rollout"
@@ -140,8 +169,9 @@ def result(env, out, names, k, K, T):
     return out
 
 
-def run(env, targets=None, tau=None, repeat=None, env_ids=None, fields=None, out=None, dt=None, iterations=None, residual_threshold=None):
-    """RexBatchEnv.rollout (documented there)."""
+def run(env, targets=None, tau=None, repeat=None, env_ids=None, fields=None, out=None, dt=None, iterations=None, residual_threshold=None,
+        init_state=None, base_wrench=None, body=None):
+    """RexBatchEnv.rollout (documented there).  With init_state, base_wrench and body all None the call is rex_rollout, else rex_rollout_from."""
     who = "rollout"
     readout.not_arm(env, who)
     if env.config.on_rack:
@@ -156,7 +186,13 @@ def run(env, targets=None, tau=None, repeat=None, env_ids=None, fields=None, out
         ids, k = env._row_ids(env_ids, who)
         commands, K, T = check_commands(env, targets, tau, k)
         repeat = check_repeat(repeat, T, int(env.config.action_repeat))
+        start = check_from(env, init_state, base_wrench, body, k, K, T)
         out = result(env, out, names, k, K, T)
         inp = _lib.RexRolloutIn(readout.ptr(targets), readout.ptr(tau), K, T, repeat, settings[0], settings[1], settings[2])
-        _lib.check(env._L.rex_rollout(env._h, readout.ptr(ids), k, ctypes.byref(inp), ctypes.byref(out.struct), env._stream_ptr()), "rex_rollout")
+        if all(t is None for t in start):
+            _lib.check(env._L.rex_rollout(env._h, readout.ptr(ids), k, ctypes.byref(inp), ctypes.byref(out.struct), env._stream_ptr()), "rex_rollout")
+        else:
+            src = _lib.RexRolloutFrom(*(readout.ptr(t) for t in start))
+            _lib.check(env._L.rex_rollout_from(env._h, readout.ptr(ids), k, ctypes.byref(inp), ctypes.byref(src), ctypes.byref(out.struct),
+                                               env._stream_ptr()), "rex_rollout_from")
     return out
