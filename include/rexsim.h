@@ -752,6 +752,76 @@ typedef struct RexRolloutFrom {      /* any member may be NULL; all NULL: rex_ro
 REX_API int rex_rollout_from(RexSim* sim, const int32_t* d_env_ids, int n, const RexRolloutIn* in, const RexRolloutFrom* from,
                              const RexRolloutOut* out, void* stream);
 
+/* The env's controller as a readout (csrc/rex_command.h): for row (k, c) = (env d_env_ids[k] or env k, candidate c) ONE control step of
+ * the env's own controller and nothing else -- what rex_step does between loading the env and its first substep: ClipAction plus
+ * RangeNormalize when cfg.range_normalize is set, the task's command (walk, gallop, turn: ik and ol; standup; poses) with its goal,
+ * brake and hold latches, then the gait planner and the inverse kinematics.  One small read-only launch that calls the step kernels' own
+ * command functions in their lane-group form (a lane per row and leg); no host sync; the sim's state is never written.
+ *   d_actions   [n][K][A], A = rex_action_dim(cfg): taken as given, as rex_step takes them (no Box check)
+ *   d_state     [n][K][37] words 0..36 of the row, or NULL: the env's.  Only position and quaternion are read (the goal tests)
+ *   d_ctrl      [n][K][8] the row's controller words REX_S_PHI .. REX_S_STEPS (37..44) as the state block holds them -- raw 32-bit
+ *               words, the ints (REX_S_LASTT, REX_S_ENDTIME, REX_S_FLAGS, REX_S_STEPS) as bit patterns --, or NULL: the env's
+ *   d_targets   [n][K][12] what d_motor_cmd / info['action'] of the step would hold, or NULL
+ *   d_ctrl_next [n][K][8] the eight words as the step would store them for an env whose step returns done = 0: with the epilogue's
+ *               REX_S_STEPS + 1 and REX_S_TARGET = fabsf(target); REX_F_DONE is never set.  Or NULL (not both outputs)
+ * Read from the env besides: REX_S_EPISODE and the config.  The controller's clock is the env's, REX_S_STEPS x cfg.action_repeat x
+ * cfg.sim_time_step.  Sensor noise is not drawn, as in every readout: the turn task's goal test sees the row's true yaw.
+ * The inputs are the caller's, so the kernel was read for arbitrary float input: no address is formed from an action, a state or a
+ * controller word -- rows are addressed by the row index and the env id, the command functions index their tables by leg and by launch
+ * constants, flag bits and (int)aux only select between constants.  A bad row -- a non-finite action, controller words that no step
+ * wrote -- yields garbage in that row only.
+ * REX_EINVAL (message in rex_last_error) without a launch for: NULL d_actions; both outputs NULL; candidates < 1; a null sim; n < 1;
+ * n > num_envs without ids; n * candidates * 37 >= 2^31; a sim of mark arm, of REX_TASK_MIXED or with the latency model on (the turn
+ * goal test would read the observation ring). */
+REX_API int rex_command(RexSim* sim, const int32_t* d_env_ids, int n, int candidates, const float* d_actions, const float* d_state,
+                        const float* d_ctrl, float* d_targets, float* d_ctrl_next, void* stream);
+
+/* Action-space rollouts: where row (k, c) is after T control steps under ACTIONS of the env's own action space (2 numbers for walk-IK
+ * and turn, 4 or 8 for the open-loop gaits) -- what shielding a policy action, sampling in the action space instead of 12 x T motor
+ * targets and scoring a policy against alternatives ask for.  The controller is closed-loop through its latches (the goal tests read
+ * base x or yaw), so targets cannot be precomputed: ONE call enqueues, for t = 0 .. T-1, rex_command on the row's current (state, ctrl)
+ * and actions[t], then rex_rollout_from with steps = 1, those targets and the previous step's state -- 2 T launches on `stream`, no host
+ * sync, no copies.  The physics IS rex_rollout_from's kernel (a rollout continued from its own `state` is the unsplit rollout bit for
+ * bit), the controller IS rex_command's: a single rex_rollout_from launch fed the emitted `targets` reproduces state, trajectory and
+ * foot_contact bit for bit.  (A controller inside the rollout launch was tried and not merged: docs/HISTORY.md.)
+ * Every per-step array is TIME-MAJOR, the convention of rex_step_segment, so each launch reads and writes a contiguous slice:
+ *   in->actions [T][n][K][A];  from->base_wrench [T][n][K][6] (time-major HERE, unlike rex_rollout_from);  from->init_state [n][K][37]
+ *   and from->body [n][K][3] as in rex_rollout_from;  in->ctrl [n][K][8] the controller words each row starts from, or NULL: the env's.
+ * candidates, steps, repeat, dt, iterations, residual_threshold: RexRolloutIn's, steps x repeat <= 4096.  repeat and dt are the
+ * PHYSICS': the controller's clock stays the env's (cfg.action_repeat x cfg.sim_time_step per control step) whatever they are.
+ * Outputs (any member may be NULL, not all):  state [n][K][37] and ctrl [n][K][8] after the last step -- feeding them to the next call
+ * as from->init_state and in->ctrl continues the rollout bit for bit;  trajectory [T][n][K][37], ctrl_trajectory [T][n][K][8], targets
+ * [T][n][K][12], foot_contact [T][n][K][4] per control step;  sweeps [T][n][K] per control step (nothing is summed across launches).
+ * Not advanced: the overheat counters and the motor mask, reward, done, resets, episode counters, sensor noise.
+ * Buffers the caller did not ask for (the state and ctrl ping-pong, one step of targets) live in d_workspace, a device buffer of at
+ * least rex_rollout_actions_workspace_bytes(n, candidates) bytes, 4-byte aligned, the caller's (-1 for n < 1, candidates < 1 or
+ * n * candidates >= 2^31).
+ * REX_EINVAL (message in rex_last_error) before any launch for everything rex_rollout_from and rex_command refuse (with on_rack,
+ * body_contacts, the latency model, mark arm, REX_TASK_MIXED), NULL in, from, out or in->actions, an `out` whose members are all NULL,
+ * and a NULL or too small workspace. */
+typedef struct RexRolloutActionsIn {
+  const float* actions;        /* [T][n][K][A] actions of the env's action space, A = rex_action_dim(cfg) */
+  const float* ctrl;           /* [n][K][8] controller words REX_S_PHI .. REX_S_STEPS each row starts from, or NULL: the env's */
+  int32_t candidates;          /* K >= 1 */
+  int32_t steps;               /* T >= 1 control steps */
+  int32_t repeat;              /* substeps per control step; <= 0: cfg.action_repeat */
+  float dt;                    /* <= 0: cfg.sim_time_step */
+  int32_t iterations;          /* <= 0: cfg.solver_iterations */
+  float residual_threshold;    /* < 0: cfg.solver_residual_threshold; 0: always `iterations` sweeps */
+} RexRolloutActionsIn;
+typedef struct RexRolloutActionsOut {   /* any member may be NULL, not all */
+  float* state;                /* [n][K][37]    words 0..36 after the last substep */
+  float* trajectory;           /* [T][n][K][37] the same after every control step */
+  uint8_t* foot_contact;       /* [T][n][K][4]  as RexRolloutOut's, per control step */
+  int32_t* sweeps;             /* [T][n][K]     solver sweeps of the control step's substeps */
+  float* ctrl;                 /* [n][K][8]     controller words after the last step */
+  float* ctrl_trajectory;      /* [T][n][K][8]  the same after every control step */
+  float* targets;              /* [T][n][K][12] the motor angle commands the controller emitted */
+} RexRolloutActionsOut;
+REX_API long long rex_rollout_actions_workspace_bytes(int n, int candidates);
+REX_API int rex_rollout_actions(RexSim* sim, const int32_t* d_env_ids, int n, const RexRolloutActionsIn* in, const RexRolloutFrom* from,
+                                const RexRolloutActionsOut* out, void* d_workspace, long long workspace_bytes, void* stream);
+
 /* The acceleration level (csrc/rex_contact_space.h): what a whole-body controller, a force-distribution QP or an analytic contact model
  * needs beside M, h and J_p -- each in one read-only launch, M(q) never written out, the state never written.  Mark base only.  Rows, ids
  * and launch as rex_dynamics: no host sync; v, the order of its 18 components, M, h, J_p, the masses (with the env's scales) and the toe

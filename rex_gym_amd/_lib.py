@@ -128,6 +128,19 @@ class RexRolloutFrom(ctypes.Structure):
     _fields_ = [("init_state", ctypes.c_void_p), ("base_wrench", ctypes.c_void_p), ("body", ctypes.c_void_p)]
 
 
+class RexRolloutActionsIn(ctypes.Structure):
+    """Mirror of `struct RexRolloutActionsIn` (include/rexsim.h): the time-major actions, the controller words the rows start from (null:
+    the env's), then the shape and the solver settings as RexRolloutIn holds them."""
+    _fields_ = [("actions", ctypes.c_void_p), ("ctrl", ctypes.c_void_p), ("candidates", ctypes.c_int32), ("steps", ctypes.c_int32),
+                ("repeat", ctypes.c_int32), ("dt", ctypes.c_float), ("iterations", ctypes.c_int32), ("residual_threshold", ctypes.c_float)]
+
+
+class RexRolloutActionsOut(ctypes.Structure):
+    """Mirror of `struct RexRolloutActionsOut` (include/rexsim.h): the device arrays rex_rollout_actions fills (a null one is skipped)."""
+    _fields_ = [("state", ctypes.c_void_p), ("trajectory", ctypes.c_void_p), ("foot_contact", ctypes.c_void_p), ("sweeps", ctypes.c_void_p),
+                ("ctrl", ctypes.c_void_p), ("ctrl_trajectory", ctypes.c_void_p), ("targets", ctypes.c_void_p)]
+
+
 class RexContactSpaceOut(ctypes.Structure):
     """Mirror of `struct RexContactSpaceOut` (include/rexsim.h): the device arrays rex_contact_space fills (a null one is skipped)."""
     _fields_ = [("delassus", ctypes.c_void_p), ("toe_drift", ctypes.c_void_p), ("toe_acc_free", ctypes.c_void_p)]
@@ -251,6 +264,10 @@ _SIGS = {
                     ctypes.c_int),
     "rex_rollout_from": ([ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(RexRolloutIn), ctypes.POINTER(RexRolloutFrom),
                           ctypes.POINTER(RexRolloutOut), ctypes.c_void_p], ctypes.c_int),
+    "rex_command": ([ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int] + [ctypes.c_void_p] * 6, ctypes.c_int),
+    "rex_rollout_actions_workspace_bytes": ([ctypes.c_int, ctypes.c_int], ctypes.c_longlong),
+    "rex_rollout_actions": ([ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(RexRolloutActionsIn), ctypes.POINTER(RexRolloutFrom),
+                             ctypes.POINTER(RexRolloutActionsOut), ctypes.c_void_p, ctypes.c_longlong, ctypes.c_void_p], ctypes.c_int),
     "rex_inverse_dynamics": ([ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(RexDynamicsLoad), ctypes.c_void_p,
                               ctypes.c_void_p], ctypes.c_int),
     "rex_contact_space": ([ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(RexContactSpaceOut),

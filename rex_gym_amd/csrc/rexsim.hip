@@ -14,6 +14,7 @@
 #include "rex_dynamics_solve.h"
 #include "rex_contact_solve.h"
 #include "rex_rollout.h"
+#include "rex_command.h"
 #include "rex_contact_space.h"
 #include "rex_force_distribution.h"
 #include "rex_visual_gen.h"
@@ -1301,6 +1302,101 @@ int rex_rollout_from(RexSim* s, const int32_t* d_env_ids, int n, const RexRollou
   if (args_err != REX_OK) return args_err;
   HIPCHK(hipSetDevice(s->device));
   HIPCHK(rex_launch_rollout_from(s, d_env_ids, n, a, *from, (hipStream_t)stream));
+  return REX_OK;
+}
+
+static_assert(sizeof(RexRolloutActionsIn) == 40 && sizeof(RexRolloutActionsOut) == 56, "RexRolloutActionsIn: two pointers, six 4-byte words; RexRolloutActionsOut: 7 pointers (rex_gym_amd/_lib.py mirrors them)");
+static_assert(offsetof(RexRolloutActionsIn, candidates) == 16 && offsetof(RexRolloutActionsIn, residual_threshold) == 36 && offsetof(RexRolloutActionsOut, ctrl) == 32 &&
+              offsetof(RexRolloutActionsOut, targets) == 48, "RexRolloutActionsIn / RexRolloutActionsOut: no padding");
+
+// what rex_command refuses of a sim beyond solve_rows (null sim, n, mark arm): the batches whose controller the readout does not restate
+static int command_sim(const char* who, const RexSim* s) {
+  if (s->cfg.task == REX_TASK_MIXED) return failf(REX_EINVAL, "%s: a REX_TASK_MIXED sim runs a task per env: single-task sims only", who);
+  if (has_latency(s->cfg))
+    return failf(REX_EINVAL, "%s: a sim with the latency model on (pd_latency or control_latency > 0) reads the turn goal test's orientation from an observation ring the readout does not restate", who);
+  return REX_OK;
+}
+
+// one rex_command_kernel over n * K rows (arguments checked by the callers); sensor noise is not drawn, as in every readout
+static hipError_t launch_command(const RexSim* s, const rex::RexCommandArgs& a, hipStream_t st) {
+  rex::DevCfg c = s->dev;
+  c.noise_on = 0;
+  c.hist = nullptr;
+  const int rows = a.n * a.K;
+  hipLaunchKernelGGL(rex::rex_command_kernel, dim3((4 * (unsigned)rows + rex::kCommandThreads - 1) / rex::kCommandThreads), dim3(rex::kCommandThreads), 0, st, c, a,
+                     (const float*)s->d_state);
+  return hipGetLastError();
+}
+
+int rex_command(RexSim* s, const int32_t* d_env_ids, int n, int candidates, const float* d_actions, const float* d_state, const float* d_ctrl,
+                float* d_targets, float* d_ctrl_next, void* stream) {
+  const char* who = "rex_command";
+  if (!d_actions) return failf(REX_EINVAL, "%s: null actions", who);
+  if (!d_targets && !d_ctrl_next) return failf(REX_EINVAL, "%s: every output pointer is null", who);
+  if (candidates < 1) return failf(REX_EINVAL, "%s: candidates %d: at least one candidate per env", who, candidates);
+  const int rows_err = solve_rows(who, s, d_env_ids, n);               // a null sim, n < 1, n > num_envs without ids, mark arm
+  if (rows_err != REX_OK) return rows_err;
+  if ((long long)n * candidates * rex::kRolloutWords >= (1ll << 31))
+    return failf(REX_EINVAL, "%s: n %d, candidates %d: n * candidates * 37 must stay below 2^31", who, n, candidates);
+  const int sim_err = command_sim(who, s);
+  if (sim_err != REX_OK) return sim_err;
+  HIPCHK(hipSetDevice(s->device));
+  HIPCHK(launch_command(s, rex::RexCommandArgs{d_actions, d_state, d_ctrl, d_targets, d_ctrl_next, nullptr, d_env_ids, n, candidates}, (hipStream_t)stream));
+  return REX_OK;
+}
+
+// per row: the state ping-pong (2 x 37 words), the controller words' ping-pong (2 x 8) and one step of targets (12)
+long long rex_rollout_actions_workspace_bytes(int n, int candidates) {
+  if (n < 1 || candidates < 1 || (long long)n * candidates >= (1ll << 31)) return -1;
+  return (long long)n * candidates * (2 * rex::kRolloutWords + 2 * rex::kCommandCtrlWords + 12) * (long long)sizeof(float);
+}
+
+int rex_rollout_actions(RexSim* s, const int32_t* d_env_ids, int n, const RexRolloutActionsIn* in, const RexRolloutFrom* from, const RexRolloutActionsOut* out,
+                        void* d_workspace, long long workspace_bytes, void* stream) {
+  const char* who = "rex_rollout_actions";
+  if (!in || !from || !out) return failf(REX_EINVAL, "%s: null pointer", who);
+  if (!in->actions) return failf(REX_EINVAL, "%s: null actions", who);
+  if (!out->state && !out->trajectory && !out->foot_contact && !out->sweeps && !out->ctrl && !out->ctrl_trajectory && !out->targets)
+    return failf(REX_EINVAL, "%s: every output pointer is null", who);
+  const long long need = rex_rollout_actions_workspace_bytes(n, in->candidates);
+  if (need > 0 && (!d_workspace || workspace_bytes < need))
+    return failf(REX_EINVAL, "%s: a workspace of %lld bytes, rex_rollout_actions_workspace_bytes(%d, %d) is %lld", who, d_workspace ? workspace_bytes : 0ll, n, in->candidates, need);
+  // the shape and the settings are RexRolloutIn's: checked, and their defaults resolved, by what rex_rollout_from checks them with
+  // (the two pointers only say "targets, and an output": every step's launch below gets its own)
+  static float probe;
+  float* const ws = (float*)d_workspace;
+  const RexRolloutIn shape{&probe, nullptr, in->candidates, in->steps, in->repeat, in->dt, in->iterations, in->residual_threshold};
+  const RexRolloutOut some{&probe, nullptr, nullptr, nullptr};
+  rex::RexRolloutArgs a;
+  const int args_err = rollout_args(who, s, d_env_ids, n, &shape, &some, a);
+  if (args_err != REX_OK) return args_err;
+  const int sim_err = command_sim(who, s);
+  if (sim_err != REX_OK) return sim_err;
+  const int K = a.K, T = a.T;
+  const size_t rows = (size_t)n * K;
+  float* const ws_state[2] = {ws, ws + rows * rex::kRolloutWords};
+  float* const ws_ctrl[2] = {ws + 2 * rows * rex::kRolloutWords, ws + 2 * rows * rex::kRolloutWords + rows * rex::kCommandCtrlWords};
+  float* const ws_targets = ws + 2 * rows * (rex::kRolloutWords + rex::kCommandCtrlWords);
+  const int A = s->dev.action_dim;
+  HIPCHK(hipSetDevice(s->device));
+  const float* state_prev = from->init_state;     // null: the env's own words 0..36
+  const float* ctrl_prev = in->ctrl;              // null: the env's own words REX_S_PHI .. REX_S_STEPS
+  a.T = 1;
+  for (int t = 0; t < T; ++t) {
+    const bool last = t == T - 1;
+    float* const tg = out->targets ? out->targets + (size_t)t * rows * 12 : ws_targets;
+    float* const cn = out->ctrl_trajectory ? out->ctrl_trajectory + (size_t)t * rows * rex::kCommandCtrlWords : (last && out->ctrl ? out->ctrl : ws_ctrl[t & 1]);
+    float* const cc = last && out->ctrl && cn != out->ctrl ? out->ctrl : nullptr;
+    HIPCHK(launch_command(s, rex::RexCommandArgs{in->actions + (size_t)t * rows * A, state_prev, ctrl_prev, tg, cn, cc, d_env_ids, n, K}, (hipStream_t)stream));
+    float* const traj = out->trajectory ? out->trajectory + (size_t)t * rows * rex::kRolloutWords : nullptr;
+    float* const st_out = last ? (out->state ? out->state : ws_state[t & 1]) : (traj ? nullptr : ws_state[t & 1]);
+    a.targets = tg;
+    a.out = RexRolloutOut{st_out, traj, out->foot_contact ? out->foot_contact + (size_t)t * rows * 4 : nullptr, out->sweeps ? out->sweeps + (size_t)t * rows : nullptr};
+    const RexRolloutFrom step{state_prev, from->base_wrench ? from->base_wrench + (size_t)t * rows * 6 : nullptr, from->body};
+    HIPCHK(rex_launch_rollout_from(s, d_env_ids, n, a, step, (hipStream_t)stream));
+    state_prev = traj ? traj : st_out;
+    ctrl_prev = cn;
+  }
   return REX_OK;
 }
 

@@ -730,6 +730,44 @@ class RexBatchEnv:
         from .. import rollout
         return rollout.run(self, targets, tau, repeat, env_ids, fields, out, dt, iterations, residual_threshold, init_state, base_wrench, body)
 
+    # ---- the controller as a readout, rollouts in the action space (rex_gym_amd/rollout_actions.py) ----
+    def command(self, actions, state=None, ctrl=None, env_ids=None, out=None):
+        """ONE control step of the env's own controller per row and nothing else (rex_command): what env.step(actions) does between
+        loading the env and its first substep -- ClipAction + RangeNormalize when range_normalize is set, the task's command with its
+        goal, brake and hold latches, the gait planner and the inverse kinematics -- in one small read-only launch of the step kernels'
+        own functions, no host sync; the state is never written.  actions: float32 device tensor [k, K, A], contiguous ([k, A]: K = 1;
+        k rows: env_ids as in render(), no env twice), taken as given as step(check_actions=False) takes them.  state [k, K, 37] (or
+        [k, 37]): the words 0..36 of the row, of which position and quaternion are read (None: the env's).  ctrl [k, K, 8] (or [k, 8]):
+        the controller words 37..44 as the state block holds them, ints as bit patterns (None: the env's).  Returns (targets [k, K, 12],
+        what info['action'] of the step would hold; ctrl [k, K, 8], the words as the step would store them for an env whose step returns
+        done = 0: steps + 1, target = |target|, REX_F_DONE never set).  out=(targets, ctrl): refilled in place.  Sensor noise is not
+        drawn: the turn goal test sees the row's true yaw.  Mark 'arm' raises NotImplementedError; mixed batches and latency-model envs
+        raise ValueError.  Every argument error is raised before any launch."""
+        from .. import rollout_actions
+        return rollout_actions.command(self, actions, state, ctrl, env_ids, out)
+
+    def rollout_actions(self, actions, repeat=None, init_state=None, ctrl=None, base_wrench=None, body=None, env_ids=None, fields=None, out=None,
+                        dt=None, iterations=None, residual_threshold=None):
+        """Where every row is after T control steps under ACTIONS of the env's own action space (rex_rollout_actions): per control step
+        command() on the row's current (state, ctrl), then rollout()'s kernel for one control step from the previous state -- 2 T
+        launches enqueued by one call on the env's device and stream, no host sync, no copies; the state is never written.  Every
+        per-step tensor is TIME-MAJOR, as in step_segment: actions float32 [T, k, K, A] ([T, k, A]: K = 1), base_wrench [T, k, K, 6].
+        init_state [k, K, 37] or [k, 37], body [k, K, 3]: as in rollout().  ctrl [k, K, 8] or [k, 8]: the controller words each row
+        starts from (None: the env's).  repeat, dt, iterations, residual_threshold: the PHYSICS' settings as in rollout() (T x repeat <=
+        4096); the controller's clock stays the env's, action_repeat x dt of the config per control step.  Returns a
+        rollout_actions.ActionRollout that unpacks like the namedtuple (state, trajectory, foot_contact, sweeps, ctrl, ctrl_trajectory,
+        targets):
+          state [k, K, 37], ctrl [k, K, 8]: after the last step -- handed back as init_state= and ctrl= they continue the rollout bit for bit
+          trajectory [T, k, K, 37], ctrl_trajectory [T, k, K, 8], targets [T, k, K, 12], foot_contact [T, k, K, 4] uint8, sweeps [T, k, K]
+              int32: per control step (sweeps is not summed over the steps)
+        with the views of rollout()'s result (base_pos, ..., joint_rates) and flags, steps: int32 views of ctrl.  A single
+        rollout(targets=ro.targets.permute(1, 2, 0, 3).contiguous(), ...) reproduces state, trajectory and foot_contact bit for bit.
+        NOT advanced: the overheat counters and the motor mask, reward, done, resets, episode counters, sensor noise.  fields, out: as
+        in kinematics(); the workspace is allocated once per shape and kept.  Refuses what command() and rollout() refuse (mark 'arm',
+        mixed, latency, on_rack, body_contacts).  Every argument error is raised before any launch."""
+        from .. import rollout_actions
+        return rollout_actions.run(self, actions, repeat, init_state, ctrl, base_wrench, body, env_ids, fields, out, dt, iterations, residual_threshold)
+
     # ---- the acceleration level (rex_gym_amd/contact_space.py) ----
     def inverse_dynamics(self, vdot=None, tau=None, toe_forces=None, base_wrench=None, env_ids=None, out=None):
         """need [k, 18] = M vdot + bias - S^T tau - sum_p J_p^T f_p - w at the current state (rex_inverse_dynamics): the equation of
