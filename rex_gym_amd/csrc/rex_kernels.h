@@ -927,8 +927,25 @@ __device__ __forceinline__ void gather_legs(const SM& sm, int leg0, EnvState& e,
 // and one-wave workgroups keep a multi-round launch (> 16 384 envs) from waiting for the slowest of four waves before a CU takes new work
 // (65 536 walk-IK envs, fused actor per step: 68.9 M env-steps/s with four-wave workgroups)
 #define REX_POLICY_WAVES(EPW) ((EPW) <= 8 ? 4 : 1)
+// The step kernels of mark 'base' take 370-510 registers a lane (256 VGPRs + 120-256 AGPRs): one wave per SIMD is all that ever runs, whatever the
+// batch.  ONE of them says so (amdgpu_waves_per_eu(1, 1)): `<4, base>` in STEP mode, the kernel behind rex_step at up to 4 096 envs -- the variant
+// on which it was measured to pay.  The attribute takes the occupancy target away from the compiler's instruction scheduling and register
+// allocation.  Same source, same arithmetic (the contraction is fixed by the source; the outputs are bit-identical), another order and
+// allocation: its row blocks come out with 283 / 281 instructions and 10 / 8 `s_nop` instead of 287 / 284 and 14 / 11; 120 AGPRs and no scratch,
+// as before.  Every other kernel -- the SEG, POL and RNN modes of 4 envs per wave (segment launches, fused actors: not measured with it), 8, 16
+// and 64 envs per wave of the base group (8: measured slower), the arm, mixed and link-box groups, the _trace instantiations -- gets (0, 0),
+// which emits no attribute at all: their ISA is the parent's, instruction for instruction.  The _trace kernels thereby keep the old schedule,
+// and their bit-identity with the product kernels checks new against old.  Measurements: profiles/critical_wave.md.
+#ifndef REX_ONE_WAVE_PER_SIMD
+/* 4 envs per wave only: with the attribute on every base kernel, 8 envs per wave measured 0.4-0.9 % SLOWER (walk-IK and gallop-OL at 8 192 envs;
+   profiles/critical_wave.md section 2), 16 made no difference.  SEG (and with it POL, RNN): the segment and closed-loop figures were never taken
+   with it, so those modes stay as they were */
+#define REX_ONE_WAVE_PER_SIMD(EPW, ARM, MIXED, BODY, TRACE, SEG) ((EPW) == 4 && !(ARM) && !(MIXED) && !(BODY) && !(TRACE) && !(SEG))
+#endif
 template <int EPW, bool ARM, bool MIXED, bool BODY, bool TRACE = false, bool SEG = false, bool POLICY = false, bool RNN = false, bool MOTOR = false>
-__global__ __launch_bounds__(POLICY && !RNN ? REX_WAVE * REX_POLICY_WAVES(EPW) : REX_WAVE) REX_STEP_KERNEL_ATTR void rex_step_kernel(DevCfg c, float* __restrict__ state, const float* __restrict__ snap,
+__global__ __launch_bounds__(POLICY && !RNN ? REX_WAVE * REX_POLICY_WAVES(EPW) : REX_WAVE)
+__attribute__((amdgpu_waves_per_eu(REX_ONE_WAVE_PER_SIMD(EPW, ARM, MIXED, BODY, TRACE, SEG) ? 1 : 0, REX_ONE_WAVE_PER_SIMD(EPW, ARM, MIXED, BODY, TRACE, SEG) ? 1 : 0)))
+REX_STEP_KERNEL_ATTR void rex_step_kernel(DevCfg c, float* __restrict__ state, const float* __restrict__ snap,
                                                             const float* __restrict__ action0, float* __restrict__ obs_out0,
                                                             float* __restrict__ reward_out0, uint8_t* __restrict__ done_out0,
                                                             float* __restrict__ cmd_out0, typename StepArg<POLICY, RNN, MOTOR>::type pol) {

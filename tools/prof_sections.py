@@ -4,9 +4,12 @@
 Builds the library with -DREX_PROF (clock64() stamps around the sections of physics_substep, accumulated per
 workgroup by lane 0) into scratch/librexsim_prof.so, runs walk-IK at N envs and prints cycles per substep for:
 leg factorisation, base Cholesky, row finishing, PGS sweeps, back-substitution + integration.
-  python tools/prof_sections.py [N=4096] [--arm] [--task=standup|poses|...] [--roll=R] [--body=0|1] [--rebuild] [--stagger] [--cert]
+  python tools/prof_sections.py [N=4096] [--arm] [--task=standup|poses|...] [--roll=R] [--body=0|1] [--rebuild] [--stagger] [--cert] [--critical[=LAUNCHES]]
 --stagger: the pre-roll of bench.py -- a random 1 / 32 of the batch reset every 50 of the first 1 300 pre-roll steps -- instead of a
            synchronised batch: the stationary episode-age mix of the headline, with freshly reset (capped) envs in it
+--critical: the critical path of a launch instead of means over workgroups: the counters are read and cleared around every one of LAUNCHES
+           (default 100) launches of the steady mix, the wave whose end (start tick + length on the 100 MHz counter) is the launch's latest is
+           picked, and ITS section split is averaged over the launches -- the cycles that move a one-launch-per-step figure.  Implies --stagger.
 --cert:    which certificate rows for the residual on demand (csrc/rex_device.h REX_CERT_ROW_MASK): a library of its own, built with
            -DREX_PROF_CERT_SETS=<CERT_SETS below> (scratch/librexsim_prof_cert.so, or REX_PROF_LIB=...), counts per candidate set the WAVE
            sweeps in which the out-of-line block would have run -- some running env of the wave left undecided
@@ -40,7 +43,8 @@ L.rex_debug_prof2.argtypes = [ctypes.c_void_p, ctypes.c_int]
 HAVE_PROF3 = hasattr(L, "rex_debug_prof3")      # (a -DREX_PROF library of a commit before the residual on demand has none: A/B runs)
 if HAVE_PROF3:
     L.rex_debug_prof3.argtypes = [ctypes.c_void_p, ctypes.c_int]
-STAGGER = "--stagger" in sys.argv
+CRITICAL = next((int(a.split("=")[1]) if "=" in a else 100 for a in sys.argv if a.startswith("--critical")), 0)
+STAGGER = "--stagger" in sys.argv or CRITICAL > 0
 args = [a for a in sys.argv[1:] if not a.startswith("--")]
 n = int(args[0]) if args else 4096
 mark = "arm" if "--arm" in sys.argv else "base"
@@ -147,6 +151,75 @@ def window(steps, label):
                       "instructions per sweep %.1f (long solves %.1f, slowest %.1f) of 36" % (mask, rows, 100 * f_all, 100 * f_l, 100 * f_w, cost(f_all), cost(f_l), cost(f_w)))
 
 
+# sections of one wave, cycles: (label, counters of that wave -> value).  o = g_prof row, o2 = g_prof2 row
+CRIT_SECTIONS = [
+    ("command: load, planner, IK", lambda o, o2: o2[3]),
+    ("substeps outside the physics: motors, observation ring", lambda o, o2: o2[4] - o[2]),
+    ("legs", lambda o, o2: o[6]),
+    ("base Cholesky, predicted velocity", lambda o, o2: o[7]),
+    ("finish rows + couplings (one loop: no stamp between them)", lambda o, o2: o[3]),
+    ("pgs outside pgs_dv: votes, parking", lambda o, o2: o[0] - o2[0] - o2[1] - o2[2]),
+    ("sweep set-up", lambda o, o2: o2[0]),
+    ("sweep loop", lambda o, o2: o2[1]),
+    ("hand-back", lambda o, o2: o2[2]),
+    ("back-substitution, integration", lambda o, o2: o[2] - o[0] - o[3] - o[6] - o[7]),
+    ("epilogue: reward, reset, observation, stores", lambda o, o2: o2[5]),
+    ("kernel entry and exit", lambda o, o2: o[8] - o2[3] - o2[4] - o2[5]),
+]
+
+
+PROF_BLOCKS = 1024      # workgroups the library's counters cover (csrc/rex_device.h g_prof: blockIdx.x < 1024)
+
+
+def critical(launches, cap_sweeps):
+    """Per launch: the wave that ended it, and its sections.  Averages over the launches, next to the mean wave of the same launches.
+    cap_sweeps: wave sweeps per step of a wave that runs every solve to the cap."""
+    epw = env._L.rex_envs_per_wave(env._h)
+    blocks = (n + epw - 1) // epw
+    # a launch of more workgroups than the counters cover could end with a wave they never saw
+    assert blocks <= PROF_BLOCKS, "--critical: %d envs at %d per wave are %d workgroups, the counters cover the first %d" % (n, epw, blocks, PROF_BLOCKS)
+    crit = np.zeros((launches, len(CRIT_SECTIONS)))
+    mean = np.zeros((launches, len(CRIT_SECTIONS)))
+    tot, sweeps, toe, span, lead = (np.zeros(launches) for _ in range(5))
+    out, out2 = np.zeros((PROF_BLOCKS, 10), np.int64), np.zeros((PROF_BLOCKS, 16), np.int64)
+    for k in range(launches):
+        torch.cuda.synchronize()
+        L.rex_debug_prof(None, 1)
+        L.rex_debug_prof2(None, 1)
+        env.step(acts[k % 8])
+        torch.cuda.synchronize()
+        L.rex_debug_prof(out.ctypes.data, 0)
+        L.rex_debug_prof2(out2.ctypes.data, 0)
+        ran = out[:, 9] > 0
+        o, o2 = out[ran].astype(float), out2[ran].astype(float)
+        end = o2[:, 7] + o2[:, 6]                       # 10 ns ticks
+        order = np.argsort(end)
+        w = order[-1]
+        crit[k] = [f(o[w], o2[w]) for _, f in CRIT_SECTIONS]
+        mean[k] = [np.mean(f(o.T, o2.T)) for _, f in CRIT_SECTIONS]
+        tot[k], sweeps[k], toe[k] = o[w, 8], o[w, 1], o2[w, 12]
+        span[k] = (end[w] - o2[:, 7].min()) / 100.0     # us from the first start to the last end
+        lead[k] = (end[w] - end[order[-2]]) / 100.0 if len(order) > 1 else 0.0
+    print("critical wave of %d launches (%d envs, %s-%s, staggered resets): the wave whose end is the launch's latest" % (launches, n, task, mark))
+    print("  its kernel %.0f cycles (mean wave %.0f); launch span first start -> last end %.1f us; it ends %.2f us behind the next-to-last wave; "
+          "%.1f wave sweeps per step (%.0f %% of the launches at the full cap of %d)" %
+          (tot.mean(), mean.sum(1).mean(), span.mean(), lead.mean(), sweeps.mean(), 100 * np.mean(sweeps >= cap_sweeps), cap_sweeps))
+    print("  %-62s %10s %7s   %10s %7s" % ("section (cycles per step, summed over its substeps)", "critical", "share", "mean wave", "share"))
+    for j, (label, _) in enumerate(CRIT_SECTIONS):
+        print("  %-62s %10.0f %6.1f %%   %10.0f %6.1f %%" % (label, crit[:, j].mean(), 100 * crit[:, j].mean() / tot.mean(), mean[:, j].mean(),
+                                                             100 * mean[:, j].mean() / mean.sum(1).mean()))
+    print("  of the sweep loop, toe-row blocks of thread 0's env (stamped inside the sweep: the stamps themselves lengthen it): %.0f cycles" % toe.mean())
+    return crit, mean
+
+
+if CRITICAL:
+    g = torch.Generator(device="cuda"); g.manual_seed(1)
+    for k in range(1500):
+        env.step(acts[k % 8])
+        if k % 50 == 0 and k < 1300:      # bench.py Rollout.preroll
+            env.reset(torch.randperm(n, device="cuda", generator=g)[: max(1, n // 32)].to(torch.int32))
+    critical(CRITICAL, 300)      # action_repeat x int(300 / action_repeat) sweeps: 5 x 60 or 6 x 50 (rex_gym_env.py:184)
+    sys.exit(0)
 window(20, "first 20 steps after reset")
 g = torch.Generator(device="cuda"); g.manual_seed(1)
 for k in range(1500):
