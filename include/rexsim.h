@@ -792,7 +792,8 @@ REX_API int rex_command(RexSim* sim, const int32_t* d_env_ids, int n, int candid
  * Outputs (any member may be NULL, not all):  state [n][K][37] and ctrl [n][K][8] after the last step -- feeding them to the next call
  * as from->init_state and in->ctrl continues the rollout bit for bit;  trajectory [T][n][K][37], ctrl_trajectory [T][n][K][8], targets
  * [T][n][K][12], foot_contact [T][n][K][4] per control step;  sweeps [T][n][K] per control step (nothing is summed across launches).
- * Not advanced: the overheat counters and the motor mask, reward, done, resets, episode counters, sensor noise.
+ * Not advanced: the overheat counters and the motor mask, resets, episode counters, sensor noise.  Reward, done and the observation of
+ * every control step: rex_rollout_actions_outcome, below.
  * Buffers the caller did not ask for (the state and ctrl ping-pong, one step of targets) live in d_workspace, a device buffer of at
  * least rex_rollout_actions_workspace_bytes(n, candidates) bytes, 4-byte aligned, the caller's (-1 for n < 1, candidates < 1 or
  * n * candidates >= 2^31).
@@ -821,6 +822,61 @@ typedef struct RexRolloutActionsOut {   /* any member may be NULL, not all */
 REX_API long long rex_rollout_actions_workspace_bytes(int n, int candidates);
 REX_API int rex_rollout_actions(RexSim* sim, const int32_t* d_env_ids, int n, const RexRolloutActionsIn* in, const RexRolloutFrom* from,
                                 const RexRolloutActionsOut* out, void* d_workspace, long long workspace_bytes, void* stream);
+
+/* The step's epilogue as a readout (csrc/rex_outcome.h): what env.step() would SAY of row (k, c) = (env d_env_ids[k] or env k, candidate
+ * c) whose control step ended in the given state -- reward, done and observation, the rest of the Gym tuple beside rex_command's targets.
+ * One small read-only launch (a lane per row and leg) that calls the step kernels' own quat_to_euler, euler_to_row2, env_observation and
+ * normalize_obs1 and restates the scalar arithmetic between them; no host sync; the sim's state is never written.
+ *   d_state        [n][K][37] words 0..36 of the row AFTER the control step, or NULL: the env's
+ *   d_ctrl         [n][K][8] the controller words REX_S_PHI .. REX_S_STEPS (37..44) after that step, as rex_command's d_ctrl_next and the
+ *                  state block hold them -- REX_S_TARGET already |target|, REX_S_STEPS already + 1, REX_F_ENV_GOAL as the command set it;
+ *                  REX_F_DONE in the input is ignored --, raw 32-bit words, or NULL: the env's
+ *   d_motor_torque [n][K][12] the OBSERVED motor torques of the control step's last substep (motor.py:116-119: the clipped PD torque, not
+ *                  the applied one and not masked by the motor enable bits), as rex_rollout_actions_outcome emits them, or NULL: zeros,
+ *                  which leaves the reward's energy term out
+ *   out->reward    [n][K]: the forward reward's four branches under forward_reward_cap, drift, shake and energy = -|sum tau_obs x qd| x
+ *                  cfg.sim_time_step with the task's weights (rex_gym_env.py:501-542); the turn, standup and poses rewards
+ *   out->done      [n][K] 0 / 1: r22 < 0.85, or the true roll / pitch / y test of gallop and standup; REX_F_ENV_GOAL except for standup;
+ *                  poses never; REX_S_STEPS >= cfg.max_episode_steps when that is set
+ *   out->obs       [n][K][rex_obs_dim(cfg)]: roll, pitch, roll rate, pitch rate, then the gallop env's MapToMinusPiToPi motor angles where
+ *                  the row carries them; RangeNormalize applied when cfg.range_normalize is set
+ * Conventions of every readout: sensor noise is not drawn; there is NO reset -- on an auto_reset env the observation is the terminal one,
+ * which rex_step never returns (it returns the next episode's first) --; nothing is written to the sim.  Read from the env besides: the
+ * config.  The inputs are the caller's, so the kernel was read for arbitrary float input: no address is formed from a state or controller
+ * word or a torque -- rows are addressed by the row index and the env id, flag bits and the step counter only enter compares.  A bad row
+ * yields garbage in that row only.
+ * REX_EINVAL (message in rex_last_error) without a launch for: NULL out or an `out` whose members are all NULL; candidates < 1; a null sim;
+ * n < 1; n > num_envs without ids; n * candidates * 37 >= 2^31; a sim of mark arm, of REX_TASK_MIXED or with the latency model on (the
+ * reward would read the delayed observation). */
+typedef struct RexOutcomeOut {   /* any member may be NULL, not all */
+  float* reward;               /* [n][K] */
+  uint8_t* done;               /* [n][K] 0 / 1 */
+  float* obs;                  /* [n][K][obs_dim] */
+} RexOutcomeOut;
+REX_API int rex_outcome(RexSim* sim, const int32_t* d_env_ids, int n, int candidates, const float* d_state, const float* d_ctrl,
+                        const float* d_motor_torque, const RexOutcomeOut* out, void* stream);
+
+/* rex_rollout_actions as a forked env: the same call, the same 2 T launches, with the full Gym tuple per control step.  Per step
+ * rex_command, then the rollout kernel's third instantiation, which keeps the observed torques of the step's last substep in registers,
+ * stores them and calls the device function of rex_outcome on the row's new state, the command's controller words and those torques --
+ * the energy term cannot be recovered from the emitted states (the pre-substep joint rates are gone).  in, from, out, the workspace and its
+ * size are rex_rollout_actions'; `out` may have every member NULL here.  outcome (time-major; any member may be NULL, not all):
+ *   reward [T][n][K], done [T][n][K], obs [T][n][K][obs_dim]: bit for bit rex_outcome on trajectory[t], ctrl_trajectory[t],
+ *   motor_torque[t];  motor_torque [T][n][K][12]: the observed torques, not masked by the motor enable bits.
+ * Rows RUN ON after done (no reset inside a rollout): the caller masks with the running OR of done.  A discounted return in torch:
+ *   alive = 1 - (done.cumsum(0) - done).clamp(max=1)                 # [T, k, K]: 1 up to and including the step that ended the episode
+ *   disc = gamma ** torch.arange(T, device=reward.device)[:, None, None]
+ *   ret = (reward * alive * disc).sum(0)                             # [k, K]
+ * REX_EINVAL before any launch for everything rex_rollout_actions refuses, a NULL outcome and an outcome whose members are all NULL. */
+typedef struct RexRolloutActionsOutcome {   /* any member may be NULL, not all */
+  float* reward;               /* [T][n][K] */
+  uint8_t* done;               /* [T][n][K] 0 / 1 */
+  float* obs;                  /* [T][n][K][obs_dim] */
+  float* motor_torque;         /* [T][n][K][12] observed torques of each control step's last substep */
+} RexRolloutActionsOutcome;
+REX_API int rex_rollout_actions_outcome(RexSim* sim, const int32_t* d_env_ids, int n, const RexRolloutActionsIn* in, const RexRolloutFrom* from,
+                                        const RexRolloutActionsOut* out, const RexRolloutActionsOutcome* outcome, void* d_workspace,
+                                        long long workspace_bytes, void* stream);
 
 /* The acceleration level (csrc/rex_contact_space.h): what a whole-body controller, a force-distribution QP or an analytic contact model
  * needs beside M, h and J_p -- each in one read-only launch, M(q) never written out, the state never written.  Mark base only.  Rows, ids

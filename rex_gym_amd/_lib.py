@@ -141,6 +141,17 @@ class RexRolloutActionsOut(ctypes.Structure):
                 ("ctrl", ctypes.c_void_p), ("ctrl_trajectory", ctypes.c_void_p), ("targets", ctypes.c_void_p)]
 
 
+class RexOutcomeOut(ctypes.Structure):
+    """Mirror of `struct RexOutcomeOut` (include/rexsim.h): the device arrays rex_outcome fills (a null one is skipped)."""
+    _fields_ = [("reward", ctypes.c_void_p), ("done", ctypes.c_void_p), ("obs", ctypes.c_void_p)]
+
+
+class RexRolloutActionsOutcome(ctypes.Structure):
+    """Mirror of `struct RexRolloutActionsOutcome` (include/rexsim.h): the time-major device arrays rex_rollout_actions_outcome fills beside
+    RexRolloutActionsOut's (a null one is skipped)."""
+    _fields_ = [("reward", ctypes.c_void_p), ("done", ctypes.c_void_p), ("obs", ctypes.c_void_p), ("motor_torque", ctypes.c_void_p)]
+
+
 class RexContactSpaceOut(ctypes.Structure):
     """Mirror of `struct RexContactSpaceOut` (include/rexsim.h): the device arrays rex_contact_space fills (a null one is skipped)."""
     _fields_ = [("delassus", ctypes.c_void_p), ("toe_drift", ctypes.c_void_p), ("toe_acc_free", ctypes.c_void_p)]
@@ -268,6 +279,11 @@ _SIGS = {
     "rex_rollout_actions_workspace_bytes": ([ctypes.c_int, ctypes.c_int], ctypes.c_longlong),
     "rex_rollout_actions": ([ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(RexRolloutActionsIn), ctypes.POINTER(RexRolloutFrom),
                              ctypes.POINTER(RexRolloutActionsOut), ctypes.c_void_p, ctypes.c_longlong, ctypes.c_void_p], ctypes.c_int),
+    "rex_outcome": ([ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                     ctypes.POINTER(RexOutcomeOut), ctypes.c_void_p], ctypes.c_int),
+    "rex_rollout_actions_outcome": ([ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(RexRolloutActionsIn), ctypes.POINTER(RexRolloutFrom),
+                                     ctypes.POINTER(RexRolloutActionsOut), ctypes.POINTER(RexRolloutActionsOutcome), ctypes.c_void_p, ctypes.c_longlong,
+                                     ctypes.c_void_p], ctypes.c_int),
     "rex_inverse_dynamics": ([ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(RexDynamicsLoad), ctypes.c_void_p,
                               ctypes.c_void_p], ctypes.c_int),
     "rex_contact_space": ([ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(RexContactSpaceOut),

@@ -28,15 +28,15 @@ GROUPS = {**{"rex_step_%s.hip" % g: g for g in GROUP_NAMES}, "rex_settle_base.hi
 # (the renderers -- rex_render, rex_render_visual -- are one kernel each, no variants; rexsim.hip last: a unity build includes it behind the
 # units whose launchers its table names)
 SOURCES = sorted(GROUPS) + ["rex_render.hip", "rex_render_mesh.hip", "rex_sense.hip", "rex_kinematics.hip", "rex_dynamics.hip",
-                            "rex_dynamics_solve.hip", "rex_contact_solve.hip", "rex_contact_space.hip", "rex_force_distribution.hip", "rex_rollout.hip", "rex_learner.hip",
+                            "rex_dynamics_solve.hip", "rex_contact_solve.hip", "rex_contact_space.hip", "rex_force_distribution.hip", "rex_rollout.hip", "rex_outcome.hip", "rex_learner.hip",
                             "rexsim.hip"]
 # units compiled into another unit's object (that unit includes them at its end): the onboard sensors ride with the collision renderer,
 # whose ray functions they cast with, and so do the kinematics and dynamics readouts, the solves with the mass matrix, the contact
-# solve, the contact-space readout, the force distribution and the candidate rollouts, which walk the renderer's forward kinematics --
-# dependencies of the library like every source, but no objects of their own
+# solve, the contact-space readout, the force distribution and the candidate rollouts, which walk the renderer's forward kinematics, and
+# the step's epilogue as a readout, whose device function the rollout kernel calls -- dependencies of the library like every source, but no objects of their own
 INCLUDED_IN = {"rex_sense.hip": "rex_render.hip", "rex_kinematics.hip": "rex_render.hip", "rex_dynamics.hip": "rex_render.hip",
                "rex_dynamics_solve.hip": "rex_render.hip", "rex_contact_solve.hip": "rex_render.hip", "rex_contact_space.hip": "rex_render.hip",
-               "rex_force_distribution.hip": "rex_render.hip", "rex_rollout.hip": "rex_render.hip"}
+               "rex_force_distribution.hip": "rex_render.hip", "rex_rollout.hip": "rex_render.hip", "rex_outcome.hip": "rex_render.hip"}
 # the modes a step unit is compiled in (csrc/rex_kernels.h RexStepMode, where the reason for each is recorded) and their object-file tags
 MODES = {"STEP": "", "TRACE": "_trace", "SEG": "_seg", "POL": "_pol", "RNN": "_rnn"}
 

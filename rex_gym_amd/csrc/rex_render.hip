@@ -143,3 +143,5 @@ hipError_t rex_launch_render(const RexSim* s, const rex::RenderCam& cam, const i
 #include "rex_force_distribution.hip"
 // candidate rollouts (rex_rollout): the same front end and contact rows, substep after substep on a private copy of the state
 #include "rex_rollout.hip"
+// the step's epilogue as a readout (rex_outcome): reward, done and observation of given rows; rex_rollout.hip calls its device function
+#include "rex_outcome.hip"

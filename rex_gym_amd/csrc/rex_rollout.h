@@ -39,3 +39,15 @@ hipError_t rex_launch_rollout(const RexSim* s, const int32_t* d_ids, int n, cons
 // (r * T + t) * 6 and from.body + r * 3; a null member leaves the env's own in place (no wrench).
 hipError_t rex_launch_rollout_from(const RexSim* s, const int32_t* d_ids, int n, const rex::RexRolloutArgs& a, const RexRolloutFrom& from,
                                    hipStream_t st);
+
+// The same once more with the step's epilogue behind every control step (rex_rollout_actions_outcome in include/rexsim.h): the kernel's
+// third instantiation.  ctrl [rows][8]: the controller words after this control step (rex_command's ctrl_next) -- per row, so the launch
+// is one control step (a.T = 1, as rex_rollout_actions launches it); outcome.reward / done [rows][T], outcome.obs [rows][T][obs_dim] and
+// motor_torque [rows][T][12], the observed torques of each control step's last substep: null members are skipped.
+hipError_t rex_launch_rollout_outcome(const RexSim* s, const int32_t* d_ids, int n, const rex::RexRolloutArgs& a, const RexRolloutFrom& from,
+                                      const float* ctrl, const RexOutcomeOut& outcome, float* motor_torque, hipStream_t st);
+
+// One rex_outcome_kernel over n * K rows (rex_outcome.hip; arguments checked by the caller): null state / ctrl: the env's, null
+// motor_torque: zeros.
+hipError_t rex_launch_outcome(const RexSim* s, const int32_t* d_ids, int n, int K, const float* state, const float* ctrl, const float* motor_torque,
+                              const RexOutcomeOut& out, hipStream_t st);

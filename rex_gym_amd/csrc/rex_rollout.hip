@@ -34,12 +34,18 @@
 //   - the loops run T, repeat and at most `iterations` times, all launch-uniform; con_sweeps leaves early on a ballot but never later.
 // A bad row yields garbage in that row only: rows share nothing but the barriers and the ballot of the sweep loop's early exit, which a
 // row that never converges can only hold to the `iterations` every row is allowed anyway.
+// With RexRolloutOutcomeLaunch it is rex_rollout_actions_outcome's: rex_rollout_from's with the step's epilogue behind every control step.
+// The observed torque of the motor model (`obs`, what rex_substep keeps as ms.tau_obs: not act x enable) of the step's last substep stays
+// in three registers; behind the substep loop's last barrier the lanes store it and call outcome_row (rex_outcome.h) on W, the row's
+// controller words after the step (ctrl + row * 8, read and never used as an address) and those torques.  Every store sits behind `live`
+// and a launch-uniform null test; outcome_row's quad sum is taken by every lane.
 // (Built as part of rex_render.hip's object, like rex_contact_solve.hip: rex_gym_amd/build.py INCLUDED_IN.)
 #include <type_traits>
 #include "rex_render_common.h"
 #include "rex_rollout.h"
 #include "rex_contact_rows.h"
 #include "rex_rollout_leg.h"
+#include "rex_outcome.h"
 
 namespace rex {
 
@@ -54,12 +60,18 @@ static_assert(REX_S_POS == 0 && REX_S_QUAT == 3 && REX_S_LINVEL == 7 && REX_S_AN
 // the kernel's argument: the launch's settings and the sim's actuator knobs; for rex_rollout_from the per-row inputs behind them
 struct RexRolloutLaunch { RexRolloutArgs a; MotDev mot; };
 struct RexRolloutFromLaunch : RexRolloutLaunch { RexRolloutFrom from; };
+struct RexRolloutOutcomeLaunch : RexRolloutFromLaunch {
+  const float* ctrl;         // [rows][8] the controller words after this control step
+  RexOutcomeOut outcome;     // reward, done [rows][T], obs [rows][T][obs_dim]; null members are skipped
+  float* motor_torque;       // [rows][T][12] or null
+};
 
 template <class Launch>
 __global__ void __launch_bounds__(kDynThreads) rex_rollout_kernel(DevCfg c, const float* __restrict__ state, const int32_t* __restrict__ ids,
                                                                   int rows_total, Launch la) {
   constexpr int NM = REX_NUM_MOTORS, NE = kDynEnvs;
-  constexpr bool FROM = std::is_same<Launch, RexRolloutFromLaunch>::value;
+  constexpr bool OUTCOME = std::is_same<Launch, RexRolloutOutcomeLaunch>::value;
+  constexpr bool FROM = std::is_same<Launch, RexRolloutFromLaunch>::value || OUTCOME;
   extern __shared__ __attribute__((aligned(16))) float s_roll[];
   const RexRolloutArgs& a = la.a;
   const int el0 = threadIdx.x >> 2, leg0 = threadIdx.x & 3, el = el0, leg = leg0;
@@ -118,6 +130,7 @@ __global__ void __launch_bounds__(kDynThreads) rex_rollout_kernel(DevCfg c, cons
       }
     }
     bool touch = false;
+    float tobs[3] = {0.0f, 0.0f, 0.0f};                              // (OUTCOME only) the observed torques of the control step's last substep
     for (int r = 0; r < a.repeat; ++r) {
       // opaque copies of the lane's row and leg: what the front end forms from them alone (table addresses, the leg's model constants) is
       // invariant over the substeps, and would otherwise be hoisted in front of the loops and carried through every solver sweep
@@ -146,6 +159,7 @@ __global__ void __launch_bounds__(kDynThreads) rex_rollout_kernel(DevCfg c, cons
           if (a.motor) motor_torque(cmd[i], q, qd, qd, mp.kp, mp.kd, mp.voltage, mp.damping, strength[i], act, obs);
           else motor_torque(cmd[i], q, qd, qd, c.kp, c.kd, act, obs);
           bf[i] = ((motor_en >> (3 * leg + i)) & 1u) ? act : 0.0f;
+          if constexpr (OUTCOME) tobs[i] = obs;
         }
       } else {
         bf[0] = cmd[0]; bf[1] = cmd[1]; bf[2] = cmd[2];
@@ -199,6 +213,20 @@ __global__ void __launch_bounds__(kDynThreads) rex_rollout_kernel(DevCfg c, cons
       }
       if (out.foot_contact) out.foot_contact[((size_t)row * a.T + t) * 4 + leg] = touch ? 1 : 0;
     }
+    if constexpr (OUTCOME) {                                         // the step's epilogue on the advanced W (behind the loop's last barrier)
+      if (la.motor_torque && live) {
+        float* d = la.motor_torque + ((size_t)row * a.T + t) * NM + 3 * leg;
+        d[0] = tobs[0]; d[1] = tobs[1]; d[2] = tobs[2];
+      }
+      if (la.outcome.reward || la.outcome.done || la.outcome.obs) {  // (the same in every thread: nobody misses the quad sum)
+        uint32_t cw[kOutcomeCtrlWords];
+#pragma unroll
+        for (int j = 0; j < kOutcomeCtrlWords; ++j) cw[j] = __float_as_uint(la.ctrl[(size_t)row * kOutcomeCtrlWords + j]);
+        Outcome o;
+        outcome_row(c, W, NE, el0, leg0, cw, tobs, o);
+        if (live) outcome_store(c, la.outcome, (size_t)row * a.T + t, leg0, o);
+      }
+    }
   }
   if (live) {
     if (out.state) {
@@ -221,4 +249,10 @@ hipError_t rex_launch_rollout_from(const RexSim* s, const int32_t* d_ids, int n,
                                    hipStream_t st) {
   const rex::RexRolloutFromLaunch la{{a, s->mot}, from};
   return rex::dyn_launch(rex::rex_rollout_kernel<rex::RexRolloutFromLaunch>, rex::kRolloutBytes, s, d_ids, n * a.K, la, st);
+}
+
+hipError_t rex_launch_rollout_outcome(const RexSim* s, const int32_t* d_ids, int n, const rex::RexRolloutArgs& a, const RexRolloutFrom& from,
+                                      const float* ctrl, const RexOutcomeOut& outcome, float* motor_torque, hipStream_t st) {
+  const rex::RexRolloutOutcomeLaunch la{{{a, s->mot}, from}, ctrl, outcome, motor_torque};
+  return rex::dyn_launch(rex::rex_rollout_kernel<rex::RexRolloutOutcomeLaunch>, rex::kRolloutBytes, s, d_ids, n * a.K, la, st);
 }

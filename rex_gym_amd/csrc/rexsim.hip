@@ -1313,7 +1313,7 @@ static_assert(offsetof(RexRolloutActionsIn, candidates) == 16 && offsetof(RexRol
 static int command_sim(const char* who, const RexSim* s) {
   if (s->cfg.task == REX_TASK_MIXED) return failf(REX_EINVAL, "%s: a REX_TASK_MIXED sim runs a task per env: single-task sims only", who);
   if (has_latency(s->cfg))
-    return failf(REX_EINVAL, "%s: a sim with the latency model on (pd_latency or control_latency > 0) reads the turn goal test's orientation from an observation ring the readout does not restate", who);
+    return failf(REX_EINVAL, "%s: a sim with the latency model on (pd_latency or control_latency > 0) reads its orientation (the turn goal test, the reward) from an observation ring the readout does not restate", who);
   return REX_OK;
 }
 
@@ -1351,13 +1351,16 @@ long long rex_rollout_actions_workspace_bytes(int n, int candidates) {
   return (long long)n * candidates * (2 * rex::kRolloutWords + 2 * rex::kCommandCtrlWords + 12) * (long long)sizeof(float);
 }
 
-int rex_rollout_actions(RexSim* s, const int32_t* d_env_ids, int n, const RexRolloutActionsIn* in, const RexRolloutFrom* from, const RexRolloutActionsOut* out,
-                        void* d_workspace, long long workspace_bytes, void* stream) {
-  const char* who = "rex_rollout_actions";
-  if (!in || !from || !out) return failf(REX_EINVAL, "%s: null pointer", who);
+static_assert(sizeof(RexOutcomeOut) == 24 && sizeof(RexRolloutActionsOutcome) == 32, "RexOutcomeOut: 3 pointers; RexRolloutActionsOutcome: 4 pointers (rex_gym_amd/_lib.py mirrors them)");
+static_assert(offsetof(RexOutcomeOut, done) == 8 && offsetof(RexOutcomeOut, obs) == 16, "RexOutcomeOut: no padding (four pointers in 32 bytes have none either)");
+
+// rex_rollout_actions (oc null) and rex_rollout_actions_outcome: the same checks and the same 2 T launches; with oc every step's rollout
+// launch is the kernel's outcome instantiation, fed the command's ctrl_next
+static int rollout_actions_run(const char* who, RexSim* s, const int32_t* d_env_ids, int n, const RexRolloutActionsIn* in, const RexRolloutFrom* from,
+                               const RexRolloutActionsOut* out, const RexRolloutActionsOutcome* oc, void* d_workspace, long long workspace_bytes, void* stream) {
   if (!in->actions) return failf(REX_EINVAL, "%s: null actions", who);
-  if (!out->state && !out->trajectory && !out->foot_contact && !out->sweeps && !out->ctrl && !out->ctrl_trajectory && !out->targets)
-    return failf(REX_EINVAL, "%s: every output pointer is null", who);
+  const bool none = !out->state && !out->trajectory && !out->foot_contact && !out->sweeps && !out->ctrl && !out->ctrl_trajectory && !out->targets;
+  if (oc ? (!oc->reward && !oc->done && !oc->obs && !oc->motor_torque) : none) return failf(REX_EINVAL, "%s: every output pointer is null", who);
   const long long need = rex_rollout_actions_workspace_bytes(n, in->candidates);
   if (need > 0 && (!d_workspace || workspace_bytes < need))
     return failf(REX_EINVAL, "%s: a workspace of %lld bytes, rex_rollout_actions_workspace_bytes(%d, %d) is %lld", who, d_workspace ? workspace_bytes : 0ll, n, in->candidates, need);
@@ -1393,10 +1396,46 @@ int rex_rollout_actions(RexSim* s, const int32_t* d_env_ids, int n, const RexRol
     a.targets = tg;
     a.out = RexRolloutOut{st_out, traj, out->foot_contact ? out->foot_contact + (size_t)t * rows * 4 : nullptr, out->sweeps ? out->sweeps + (size_t)t * rows : nullptr};
     const RexRolloutFrom step{state_prev, from->base_wrench ? from->base_wrench + (size_t)t * rows * 6 : nullptr, from->body};
-    HIPCHK(rex_launch_rollout_from(s, d_env_ids, n, a, step, (hipStream_t)stream));
+    if (oc) {
+      const RexOutcomeOut oo{oc->reward ? oc->reward + (size_t)t * rows : nullptr, oc->done ? oc->done + (size_t)t * rows : nullptr,
+                             oc->obs ? oc->obs + (size_t)t * rows * (size_t)s->dev.obs_dim : nullptr};
+      HIPCHK(rex_launch_rollout_outcome(s, d_env_ids, n, a, step, cn, oo, oc->motor_torque ? oc->motor_torque + (size_t)t * rows * 12 : nullptr, (hipStream_t)stream));
+    } else HIPCHK(rex_launch_rollout_from(s, d_env_ids, n, a, step, (hipStream_t)stream));
     state_prev = traj ? traj : st_out;
     ctrl_prev = cn;
   }
+  return REX_OK;
+}
+
+int rex_rollout_actions(RexSim* s, const int32_t* d_env_ids, int n, const RexRolloutActionsIn* in, const RexRolloutFrom* from, const RexRolloutActionsOut* out,
+                        void* d_workspace, long long workspace_bytes, void* stream) {
+  const char* who = "rex_rollout_actions";
+  if (!in || !from || !out) return failf(REX_EINVAL, "%s: null pointer", who);
+  return rollout_actions_run(who, s, d_env_ids, n, in, from, out, nullptr, d_workspace, workspace_bytes, stream);
+}
+
+// (obs_dim <= 16 < 37: the outcome arrays stay below the n * K * T * 37 that rollout_args holds under 2^31)
+int rex_rollout_actions_outcome(RexSim* s, const int32_t* d_env_ids, int n, const RexRolloutActionsIn* in, const RexRolloutFrom* from, const RexRolloutActionsOut* out,
+                                const RexRolloutActionsOutcome* outcome, void* d_workspace, long long workspace_bytes, void* stream) {
+  const char* who = "rex_rollout_actions_outcome";
+  if (!in || !from || !out || !outcome) return failf(REX_EINVAL, "%s: null pointer", who);
+  return rollout_actions_run(who, s, d_env_ids, n, in, from, out, outcome, d_workspace, workspace_bytes, stream);
+}
+
+int rex_outcome(RexSim* s, const int32_t* d_env_ids, int n, int candidates, const float* d_state, const float* d_ctrl, const float* d_motor_torque,
+                const RexOutcomeOut* out, void* stream) {
+  const char* who = "rex_outcome";
+  if (!out) return failf(REX_EINVAL, "%s: null pointer", who);
+  if (!out->reward && !out->done && !out->obs) return failf(REX_EINVAL, "%s: every output pointer is null", who);
+  if (candidates < 1) return failf(REX_EINVAL, "%s: candidates %d: at least one candidate per env", who, candidates);
+  const int rows_err = solve_rows(who, s, d_env_ids, n);               // a null sim, n < 1, n > num_envs without ids, mark arm
+  if (rows_err != REX_OK) return rows_err;
+  if ((long long)n * candidates * rex::kRolloutWords >= (1ll << 31))
+    return failf(REX_EINVAL, "%s: n %d, candidates %d: n * candidates * 37 must stay below 2^31", who, n, candidates);
+  const int sim_err = command_sim(who, s);
+  if (sim_err != REX_OK) return sim_err;
+  HIPCHK(hipSetDevice(s->device));
+  HIPCHK(rex_launch_outcome(s, d_env_ids, n, candidates, d_state, d_ctrl, d_motor_torque, *out, (hipStream_t)stream));
   return REX_OK;
 }
 

@@ -762,11 +762,34 @@ class RexBatchEnv:
               int32: per control step (sweeps is not summed over the steps)
         with the views of rollout()'s result (base_pos, ..., joint_rates) and flags, steps: int32 views of ctrl.  A single
         rollout(targets=ro.targets.permute(1, 2, 0, 3).contiguous(), ...) reproduces state, trajectory and foot_contact bit for bit.
-        NOT advanced: the overheat counters and the motor mask, reward, done, resets, episode counters, sensor noise.  fields, out: as
+        Named in fields= beside them (never computed otherwise; fields=None stays those seven), the step's epilogue per control step, in
+        the same 2 T launches (rex_rollout_actions_outcome): reward [T, k, K], done [T, k, K] uint8, obs [T, k, K, obs_dim] -- bit for
+        bit outcome(trajectory[t], ctrl_trajectory[t], motor_torque[t]) -- and motor_torque [T, k, K, 12], the observed motor torques
+        of each step's last substep (not masked by the motor enable bits).  Rows run on after done: mask with the running OR of done
+        (rex_gym_amd/rollout_actions.py shows a discounted return in three lines).
+        NOT advanced: the overheat counters and the motor mask, resets, episode counters, sensor noise.  fields, out: as
         in kinematics(); the workspace is allocated once per shape and kept.  Refuses what command() and rollout() refuse (mark 'arm',
         mixed, latency, on_rack, body_contacts).  Every argument error is raised before any launch."""
         from .. import rollout_actions
         return rollout_actions.run(self, actions, repeat, init_state, ctrl, base_wrench, body, env_ids, fields, out, dt, iterations, residual_threshold)
+
+    # ---- the step's epilogue as a readout (rex_gym_amd/outcome.py) ----
+    def outcome(self, state=None, ctrl=None, motor_torque=None, env_ids=None, fields=None, out=None):
+        """What env.step() would SAY of a row whose control step ended in the given state (rex_outcome): reward, done and observation in
+        one small read-only launch of the step kernels' own functions, no host sync; the state is never written.  state [k, K, 37] (or
+        [k, 37]): the words 0..36 AFTER the control step (None: the env's).  ctrl [k, K, 8] (or [k, 8]): the controller words 37..44
+        after it, as command()'s second result and the state block hold them -- target already |target|, steps already + 1; the done flag
+        in them is ignored (None: the env's).  motor_torque [k, K, 12] (or [k, 12]): the OBSERVED motor torques of the step's last
+        substep, as rollout_actions' motor_torque holds them (None: zeros -- the reward's energy term is left out).  k rows: env_ids
+        as in render(), no env twice.  Returns an outcome.Outcome with reward [k, K], done [k, K] uint8, obs [k, K, obs_dim] -- [k],
+        [k], [k, obs_dim] when no input carries a candidate axis --: the forward reward's branches under forward_reward_cap, drift, shake
+        and energy = -|sum tau x qd| x dt, or the turn, standup, poses reward; r22 < 0.85 or the gallop / standup roll-pitch-y test, the
+        goal flag, max_episode_steps; roll, pitch and their rates, the gallop env's motor angles, RangeNormalize when range_normalize is
+        set.  Sensor noise is not drawn; there is NO reset: on an auto_reset env obs is the terminal observation, which step() never
+        returns.  fields, out: as in kinematics().  Mark 'arm' raises NotImplementedError; mixed batches and latency-model envs raise
+        ValueError.  Every argument error is raised before any launch."""
+        from .. import outcome
+        return outcome.run(self, state, ctrl, motor_torque, env_ids, fields, out)
 
     # ---- the acceleration level (rex_gym_amd/contact_space.py) ----
     def inverse_dynamics(self, vdot=None, tau=None, toe_forces=None, base_wrench=None, env_ids=None, out=None):

@@ -17,8 +17,16 @@ per control step rex_command on the row's current (state, ctrl), then the rollou
 with no host sync and no copies between them.  The physics is env.rollout's kernel, the controller the step kernels' own functions.
 The controller's clock is the env's (action_repeat x dt of the config) whatever `repeat` and `dt` the physics is given.
 
-Not advanced: the overheat counters and the motor mask, reward, done, resets, episode counters, sensor noise (the turn goal test sees the
-row's true yaw).  The env's state is never written."""
+    ro = env.rollout_actions(actions, fields=("state", "ctrl", "reward", "done", "obs", "motor_torque"))      # the forked env: what the env
+    ro.reward, ro.done, ro.obs, ro.motor_torque            # would SAY per control step -- [T, k, K], [T, k, K] uint8, [T, k, K, obs_dim] -- and
+                                                           # [T, k, K, 12] the observed motor torques of each step's last substep; computed
+                                                           # only when named (rex_rollout_actions_outcome: the same 2 T launches)
+    alive = 1 - (ro.done.cumsum(0) - ro.done).clamp(max=1) # rows run on after done: mask with the running OR of done --
+    disc = gamma ** torch.arange(T, device=ro.reward.device)[:, None, None]
+    ret = (ro.reward * alive * disc).sum(0)                # -- a discounted return per candidate, [k, K]
+
+Not advanced: the overheat counters and the motor mask, resets, episode counters, sensor noise (the turn goal test sees the row's true
+yaw).  The env's state is never written."""
 import ctypes
 
 import numpy as np
@@ -33,11 +41,15 @@ FIELDS = {"state": (False, (WORDS,), "float32"), "trajectory": (True, (WORDS,), 
           "sweeps": (True, (), "int32"), "ctrl": (False, (CTRL,), "float32"), "ctrl_trajectory": (True, (CTRL,), "float32"),
           "targets": (True, (12,), "float32")}
 assert list(FIELDS) == [f[0] for f in _lib.RexRolloutActionsOut._fields_]
+# the step's epilogue per control step (rex_rollout_actions_outcome): computed only when named in fields=; None: the env's obs_dim
+OUTCOME_FIELDS = {"reward": (True, (), "float32"), "done": (True, (), "uint8"), "obs": (True, (None,), "float32"), "motor_torque": (True, (12,), "float32")}
+assert list(OUTCOME_FIELDS) == [f[0] for f in _lib.RexRolloutActionsOutcome._fields_]
+ALL_FIELDS = {**FIELDS, **OUTCOME_FIELDS}
 
 
-def field_shape(name, k, K, T):
-    major, tail, _ = FIELDS[name]
-    return ((T,) if major else ()) + (k, K) + tail
+def field_shape(name, k, K, T, obs_dim=None):
+    major, tail, _ = ALL_FIELDS[name]
+    return ((T,) if major else ()) + (k, K) + tuple(obs_dim if d is None else d for d in tail)
 
 
 def workspace_floats(k, K):
@@ -86,6 +98,24 @@ class ActionRollout(readout.Result):
     joint_rates = property(lambda self: self._words(25, 37, "joint_rates"), doc="[k, K, 12] motor order")
     flags = property(lambda self: self._ctrl_word(CTRL_FLAGS, "flags"), doc="[k, K] int32 view of ctrl: the REX_F_* bits after the last step")
     steps = property(lambda self: self._ctrl_word(CTRL_STEPS, "steps"), doc="[k, K] int32 view of ctrl: env steps of the episode after the last step")
+
+
+class ActionOutcomeRollout(ActionRollout):
+    """The result of a rollout_actions call that names one of reward, done, obs, motor_torque: an ActionRollout -- it unpacks like the same
+    seven-tuple, `struct` is the RexRolloutActionsOut of those seven -- with the four fields beside them and `outcome_struct`, the
+    RexRolloutActionsOutcome the call was given."""
+    FIELDS = ALL_FIELDS
+
+    def __init__(self, tensors, rows, candidates, horizon):
+        self.fields = tuple(n for n in ALL_FIELDS if n in tensors)
+        for n in ALL_FIELDS:
+            setattr(self, n, tensors.get(n))
+        self.struct = _lib.RexRolloutActionsOut(**{n: t.data_ptr() for n, t in tensors.items() if n in FIELDS})
+        self.outcome_struct = _lib.RexRolloutActionsOutcome(**{n: t.data_ptr() for n, t in tensors.items() if n in OUTCOME_FIELDS})
+        self.rows, self.candidates, self.horizon = rows, candidates, horizon
+
+    def pointer(self, name):
+        return getattr(self.outcome_struct if name in OUTCOME_FIELDS else self.struct, name)
 
 
 def as_int32(ctrl):
@@ -180,15 +210,17 @@ def result(env, out, names, k, K, T):
     """out=None: a new result of empty tensors.  Else the caller's, checked unless it is the one checked last on this env with the same
     fields and shape -- a per-step read with out= allocates and validates nothing."""
     torch, who = env._torch, "rollout_actions"
+    cls = ActionOutcomeRollout if any(n in OUTCOME_FIELDS for n in names) else ActionRollout
+    shape_of = lambda n: field_shape(n, k, K, T, getattr(env, "obs_dim", None))
     if out is None:
-        return ActionRollout({n: torch.empty(field_shape(n, k, K, T), dtype=getattr(torch, FIELDS[n][2]), device=env.device) for n in names}, k, K, T)
+        return cls({n: torch.empty(shape_of(n), dtype=getattr(torch, ALL_FIELDS[n][2]), device=env.device) for n in names}, k, K, T)
     if out is not env.__dict__.get("_rollout_actions_out") or out.fields != names or (out.rows, out.candidates, out.horizon) != (k, K, T):
-        if not isinstance(out, ActionRollout) or out.fields != names:
+        if type(out) is not cls or out.fields != names:
             raise ValueError(f"{who}: out must be a result of {who}() with the fields {names}")
         for n in names:
-            t, shape, dtype = getattr(out, n), field_shape(n, k, K, T), FIELDS[n][2]
+            t, shape, dtype = getattr(out, n), shape_of(n), ALL_FIELDS[n][2]
             if not (isinstance(t, torch.Tensor) and t.dtype == getattr(torch, dtype) and t.device == env.device and tuple(t.shape) == shape
-                    and t.is_contiguous() and t.data_ptr() == getattr(out.struct, n)):
+                    and t.is_contiguous() and t.data_ptr() == (out.pointer(n) if cls is ActionOutcomeRollout else getattr(out.struct, n))):
                 raise ValueError(f"{who}: out.{n} must be the contiguous {dtype} tensor of shape {shape} on {env.device} the result was made with")
         out.rows, out.candidates, out.horizon = k, K, T
         env._rollout_actions_out = out
@@ -209,7 +241,8 @@ def run(env, actions, repeat=None, init_state=None, ctrl=None, base_wrench=None,
     """RexBatchEnv.rollout_actions (documented there)"""
     who = "rollout_actions"
     check_sim(env, who, physics=True)
-    names = readout.check_fields(FIELDS, who, fields)
+    # fields=None: the seven of rex_rollout_actions, as ever; the step's epilogue is computed only where it is named
+    names = readout.check_fields(FIELDS if fields is None else ALL_FIELDS, who, fields)
     try:
         settings = rollout.check_settings(dt, iterations, residual_threshold)
     except ValueError as e:
@@ -231,6 +264,11 @@ def run(env, actions, repeat=None, init_state=None, ctrl=None, base_wrench=None,
         ws = workspace(env, k, K)
         inp = _lib.RexRolloutActionsIn(a.data_ptr(), readout.ptr(ctrl), K, T, repeat, settings[0], settings[1], settings[2])
         src = _lib.RexRolloutFrom(readout.ptr(init_state), readout.ptr(base_wrench), readout.ptr(body))
-        _lib.check(env._L.rex_rollout_actions(env._h, readout.ptr(ids), k, ctypes.byref(inp), ctypes.byref(src), ctypes.byref(out.struct), ws.data_ptr(),
-                                              ws.numel() * 4, env._stream_ptr()), "rex_rollout_actions")
+        if isinstance(out, ActionOutcomeRollout):
+            _lib.check(env._L.rex_rollout_actions_outcome(env._h, readout.ptr(ids), k, ctypes.byref(inp), ctypes.byref(src), ctypes.byref(out.struct),
+                                                          ctypes.byref(out.outcome_struct), ws.data_ptr(), ws.numel() * 4, env._stream_ptr()),
+                       "rex_rollout_actions_outcome")
+        else:
+            _lib.check(env._L.rex_rollout_actions(env._h, readout.ptr(ids), k, ctypes.byref(inp), ctypes.byref(src), ctypes.byref(out.struct), ws.data_ptr(),
+                                                  ws.numel() * 4, env._stream_ptr()), "rex_rollout_actions")
     return out
